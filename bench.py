@@ -6,6 +6,12 @@ top-k over a 10M-doc synthetic Zipf corpus, 1/2/4/8 GPUs.
 
   python bench.py --gpus N --steps K --warmup W          # N > 1: spawns one rank per GPU itself
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   # or is launched as ranks
+  python bench.py ... --full                             # + every comparison leg, CPU baseline, parity, PMC (below)
+  python bench.py ... --dump-outputs DIR                 # + the main leg's last-step top-k as DIR/*.npy
+
+A plain run (no --full) sets up, warms up, times exactly --steps steps of the main leg (one region), writes the outputs
+if asked and prints the headline line (metric, value, unit, ms_per_step, ... and the config).  Everything else below --
+the other legs, the repeated regions, the CPU baseline and the parity checks, the PMC child runs -- needs --full.
 
 Either way every rank is one process on one GPU that reads RANK / LOCAL_RANK / WORLD_SIZE from the
 environment; the ranks find each other through a 128-byte id file and everything collective -- global df,
@@ -26,10 +32,11 @@ statistics); every rank scores every query of a batch on its docs.  The main reg
 (`"scaling": "strong"`: value(N) / value(1) is a like-for-like speed-up), and a WIDE batch of 2048 queries per step is timed
 beside it at every N, N = 1 included (`wide_batch`: wide_batch(N) / wide_batch(1) is the same-batch speed-up of a
 deployment that batches wider -- a rank's device work per step shrinks with N, the host's cost per batch does not).  The
-timed region of --steps steps is repeated --repeats times (5): `value` is the median region, min / max are in `repeats`.
+timed region of --steps steps is repeated --repeats times (1; 5 with --full): `value` is the median region, min / max are in `repeats`.
 The index is resident in HBM before the timed region.  Rank 0 prints one JSON line.
 
-Legs (all on the same resident index; only the first is `value`):
+Legs (all on the same resident index; only the first is `value`, and only the first is timed without --full -- the batches and
+the phrase side's index of the others are made all the same, so that the main leg runs in the device state it always had):
   main (fresh)      8 rotating BASELINE-shaped query sets (256 x 4 terms, one rank from each of 1-10 / 11-100 /
                     101-1000 / 1001-10000; set 0 is THE BASELINE set, seed 42) through the library's DEFAULT route for
                     the batch's shape (round 6, k <= 32: the staged-tile route; `roofline.route` names it): the exact top-k of
@@ -99,7 +106,16 @@ def parse_args():
     ap.add_argument("--scaled-queries", type=int, default=2048,
                     help="queries per step of the wide_batch leg, timed at EVERY N beside the main stream (0: off)")
     ap.add_argument("--batch-mult", type=int, default=1, help=argparse.SUPPRESS)
-    ap.add_argument("--repeats", type=int, default=5, help="timed regions of --steps steps each; value = the median region")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions of --steps steps each; value = the median region (default: 1, with --full 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the comparison legs (replay, wide batch, exhaustive overlay, dynamic pruning, "
+                         "distinct terms, dense score, phrase / slop batches), the CPU baseline and parity checks, the PMC child runs "
+                         "and 5 timed regions of the main leg.  Without it a run times the main leg's --steps steps once and prints the "
+                         "headline line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the main leg's last step returned (top-k scores float32 [B][k], doc ids "
+                         "as float64 [B][k]) as DIR/scores.npy and DIR/docs.npy")
     ap.add_argument("--weak", action="store_true", help="N > 1: N x --queries per step in the main region (default: --queries at every N)")
     ap.add_argument("--strong", action="store_true", help=argparse.SUPPRESS)     # (round 3's switch; the default now)
     ap.add_argument("--pipeline", type=int, default=6, help="batch objects (= batches in flight, one stream each) of the main leg")
@@ -328,6 +344,7 @@ class Rank:
             self.barrier()
             dts.append(self.allmax(time.perf_counter() - t0))
             i0 += n_steps
+        self.last_step = i0 - 1                               # (its set: last_step mod len(sets))
         return dts, results
 
     def timed_fresh(self, ring, sets, n_warm, n_steps, repeats=1):
@@ -371,6 +388,7 @@ class Rank:
             self.barrier()
             dts.append(self.allmax(time.perf_counter() - t0))
             i0 += n_steps
+        self.last_step = i0 - 1                               # (its set: last_step mod len(sets))
         return dts, results
 
     def close(self):
@@ -635,6 +653,7 @@ def run_pmc_children(args, leg_names, corpus):
                    sys.executable, os.path.abspath(__file__), "--pmc-child", pname, "--docs", str(args.docs),
                    "--vocab", str(args.vocab), "--queries", str(args.queries), "--k", str(args.k), "--tile", str(args.tile),
                    "--no-cpu-baseline", "--no-pmc", "--corpus-cache", cache, "--phrase-docs", str(args.phrase_docs)]
+            cmd.append("--full")                              # (the child builds every leg's batch)
             if args.no_phrase_legs:
                 cmd.append("--no-phrase-legs")
             env = dict(os.environ, TMPDIR="/tmp")
@@ -861,6 +880,35 @@ def cpu_baseline(r, queries, scores, docs, extra=()):
     return out, verdict, n_warm
 
 
+def comm_library(api):
+    """(version, path) of the collectives library the process loaded, or (None, the error)"""
+    from searcharray_amd.device_index import DeviceIndex
+    try:
+        return DeviceIndex.comm_library_info(api)
+    except Exception as e:                               # noqa: BLE001
+        return None, f"{type(e).__name__}: {e}"
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, scores, docs):
+    """What a caller of the main leg receives from its last step: top-k scores float32 [B][k] and doc ids [B][k] (uint64 in the
+    library, written as float64: exact below 2^53).  Above DUMP_LIMIT_BYTES in all, a fixed seeded sample of the queries (rows)
+    is written, its row indices as rows.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    scores = np.asarray(scores, dtype=np.float32)
+    docs = np.asarray(docs, dtype=np.float64)
+    row_bytes = scores.shape[1] * (4 + 8)
+    if scores.nbytes + docs.nbytes > DUMP_LIMIT_BYTES:
+        n = max(1, (DUMP_LIMIT_BYTES - (1 << 20)) // max(row_bytes, 1))
+        rows = np.sort(np.random.default_rng(0).choice(scores.shape[0], size=n, replace=False))
+        scores, docs = scores[rows], docs[rows]
+        np.save(os.path.join(out_dir, "rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "scores.npy"), np.ascontiguousarray(scores))
+    np.save(os.path.join(out_dir, "docs.npy"), np.ascontiguousarray(docs))
+
+
 def sharded_parity(r, queries, scores, docs, n_check=8):
     """N > 1: every rank scores the first n_check queries on ITS doc range with the CPU oracle (global df / avgdl /
     corpus size, the reference's op order), the per-shard top-k lists travel through the library's all-reduce (one slot
@@ -920,6 +968,7 @@ def main():
     mult = max(world, args.batch_mult)                      # (--batch-mult: the N > 1 batch logic on one GPU, for testing)
     weak = mult > 1 and args.weak
     B = Bq * mult if weak else Bq
+    full = args.full
     r.generate()
     phrase_legs_on = world == 1 and not r.use_comm and not args.no_phrase_legs
     leg_names = ["main", "exhaustive_overlay", "dynamic_pruning"] + (["distinct_terms"] if 4 * B <= V else []) + \
@@ -928,7 +977,7 @@ def main():
     # BEFORE this process touches the GPU (one process on the device at a time, as in a stand-alone rocprofv3
     # run); the children read the corpus this process just generated instead of generating it again.
     pmc, pmc_err = {}, "skipped"
-    if rank == 0 and world == 1 and not args.no_pmc and not args.pmc_child:
+    if full and rank == 0 and world == 1 and not args.no_pmc and not args.pmc_child:
         t0 = time.time()
         pmc, pmc_err = run_pmc_children(args, leg_names, r.corpus)
         log(rank, f"PMC child runs: {'ok' if pmc else pmc_err} ({time.time()-t0:.0f}s)")
@@ -942,7 +991,10 @@ def main():
         return np.concatenate(blocks)[:n]
     sets = [query_set(i, B) for i in range(n_sets)]
     queries = sets[0]
-    batch = r.make_batch(queries)
+    # The other legs' batches and the phrase side's index are made before the main leg in a plain run too (they are only USED with
+    # --full): the main leg is timed in the device state it always had.  The streams they own change how the runtime spreads the
+    # main leg's streams over its hardware queues, and without them the same steps run ~5-10 % slower.
+    batch = r.make_batch(queries, check=full)
     q_distinct = synth.bm25_queries_distinct(B, vocab=V) if 4 * B <= V else None
     batch_d = r.make_batch(q_distinct) if q_distinct is not None else None
     side = None
@@ -980,15 +1032,55 @@ def main():
     if args.pruned:
         route.set(sparse=1)
     P = max(1, args.pipeline if B <= 1024 else min(args.pipeline, 4))
-    pair = [r.make_batch(sets[i % len(sets)], check=(i == 0)) for i in range(P)]
-    R = max(1, args.repeats)
+    pair = [r.make_batch(sets[i % len(sets)], check=(full and i == 0)) for i in range(P)]
+    R = max(1, args.repeats if args.repeats is not None else (5 if full else 1))
     if args.driver == "queue":
         qq = r.index.queue(B, sets[0].shape[1], k=args.k, depth=P)
         dts, fresh_results = r.timed_fresh_queue(qq, sets, max(W, P), K, repeats=R)
+        fresh_route = qq.last_route(r.last_step % P)
         qq.close()
     else:
         dts, fresh_results = r.timed_fresh(pair, sets, max(W, P), K, repeats=R)
+        fresh_route = pair[r.last_step % P].last_route()
     dt = float(np.median(dts))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *fresh_results[r.last_step % len(sets)])
+    qps = B * K / dt
+
+    def headline(main_route, comm_lib):
+        """the keys of the result line that a plain run prints too"""
+        return {
+            "metric": "queries/sec, 4-term disjunctive BM25 + top-k over 10M synthetic Zipf docs",
+            "value": round(qps, 2), "unit": "queries/s", "n_gpus": world, "steps": K, "warmup": W,
+            "ms_per_step": round(dt / K * 1e3, 4), "higher_is_better": True, "scaling": "weak" if weak else "strong",
+            "repeats": {"regions": R, "steps_per_region": K, "value_from": "median region",
+                        "ms_per_step_min": round(min(dts) / K * 1e3, 4), "ms_per_step_median": round(dt / K * 1e3, 4),
+                        "ms_per_step_max": round(max(dts) / K * 1e3, 4)},
+            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": f"zipf-{D} (V={V}, Poisson(32) doc lengths, seed 1234) sharded by doc-id range, "
+                                   f"FRESH batches: {len(sets)} rotating seeded sets of {B} x 4-term disjunctive BM25 queries "
+                                   f"(k1=1.2 b=0.75; {'the first ' + str(Bq) + ' of ' if B > Bq else ''}set 0 = the BASELINE set"
+                                   f"{'; ' + str(Bq) + ' queries per GPU and step: every rank scores all of them on its docs' if weak else ''}), "
+                                   f"one sa_batch_step (idf gathered from the index table, reset, run) + fetch per step, "
+                                   f"top-{args.k}, the library's default route for the shape: {main_route}",
+                       "docs": D, "queries_per_step": B, "terms_per_query": 4, "k": args.k, "query_sets": len(sets),
+                       "batches_in_flight": P, "driver": args.driver,
+                       "distinct_terms_in_batch": int(len(np.unique(queries))),
+                       "tile_docs": int(r.info.tile_docs), "parallelism": f"doc-range shards x{world}",
+                       "collective": r.collective, "collective_library": dict(zip(("nccl_version", "path"), comm_lib)),
+                       "launcher": "torch-free: ranks rendezvous through an id file, "
+                                                               "collectives = libsearcharray_hip.so's RCCL communicator"},
+        }
+
+    if not full:
+        if rank == 0:
+            print(json.dumps(headline(fresh_route, comm_library(r.api))), flush=True)
+        for b in pair + [batch] + ([batch_d] if batch_d is not None else []):
+            b.close()
+        if side is not None:
+            side.close()
+        r.close()
+        return
     # (HIP events around one batch's scoring kernels: with P batches in flight on P streams they overlap the other
     #  batches' kernels, so this is a batch's latency share, not the device time per step -- the replay leg's is)
     kernel_ms_fresh = float(np.mean([b.profile()[0] for b in pair])) if args.driver == "ring" else float("nan")     # (the queue's batches are its own)
@@ -1056,8 +1148,6 @@ def main():
     else:
         route.unset("sparse")
 
-    qps = B * K / dt
-
     cpu, parity = None, "skipped"
     if rank == 0 and world == 1 and not r.use_comm and not args.no_cpu_baseline:
         extra = [(f"set {si}", sets[si], fresh_results[si][0], fresh_results[si][1], [1, B // 2, B - 1])
@@ -1115,11 +1205,7 @@ def main():
     if cpu is not None:
         cpu["parity"] = parity                               # (inside cpu_baseline too: the checker that timed it is the one that compared)
     if rank == 0:
-        from searcharray_amd.device_index import DeviceIndex
-        try:
-            comm_lib = DeviceIndex.comm_library_info(r.api)
-        except Exception as e:                               # noqa: BLE001
-            comm_lib = (None, f"{type(e).__name__}: {e}")
+        comm_lib = comm_library(r.api)
         n_tiles = int(r.info.n_tiles)
         comp = compulsory_bytes(r.df if world == 1 else r.index.docfreqs(), queries, B, args.k)
         main_note = ("the library's default route for this batch shape -- " + main_route + " -- exact top-k, results identical to scoring every "
@@ -1156,27 +1242,8 @@ def main():
                    "note": "the resident set 0 replayed (compare with `replay`, not with `value`)"}
         other = {"value": round(B * K2 / dt2, 2), "unit": "queries/s", "steps": K2, "ms_per_step": round(dt2 / K2 * 1e3, 4),
                  "roofline": prn_block, "same_results": same}
-        out = {
-            "metric": "queries/sec, 4-term disjunctive BM25 + top-k over 10M synthetic Zipf docs",
-            "value": round(qps, 2), "unit": "queries/s", "n_gpus": world, "steps": K, "warmup": W,
-            "ms_per_step": round(dt / K * 1e3, 4), "higher_is_better": True, "scaling": "weak" if weak else "strong",
-            "repeats": {"regions": R, "steps_per_region": K, "value_from": "median region",
-                        "ms_per_step_min": round(min(dts) / K * 1e3, 4), "ms_per_step_median": round(dt / K * 1e3, 4),
-                        "ms_per_step_max": round(max(dts) / K * 1e3, 4)},
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"zipf-{D} (V={V}, Poisson(32) doc lengths, seed 1234) sharded by doc-id range, "
-                                   f"FRESH batches: {len(sets)} rotating seeded sets of {B} x 4-term disjunctive BM25 queries "
-                                   f"(k1=1.2 b=0.75; {'the first ' + str(Bq) + ' of ' if B > Bq else ''}set 0 = the BASELINE set"
-                                   f"{'; ' + str(Bq) + ' queries per GPU and step: every rank scores all of them on its docs' if weak else ''}), "
-                                   f"one sa_batch_step (idf gathered from the index table, reset, run) + fetch per step, "
-                                   f"top-{args.k}, the library's default route for the shape: {main_route}",
-                       "docs": D, "queries_per_step": B, "terms_per_query": 4, "k": args.k, "query_sets": len(sets),
-                       "batches_in_flight": P, "driver": args.driver,
-                       "distinct_terms_in_batch": int(len(np.unique(queries))),
-                       "tile_docs": int(r.info.tile_docs), "parallelism": f"doc-range shards x{world}",
-                       "collective": r.collective, "collective_library": dict(zip(("nccl_version", "path"), comm_lib)),
-                       "launcher": "torch-free: ranks rendezvous through an id file, "
-                                                               "collectives = libsearcharray_hip.so's RCCL communicator"},
+        out = headline(main_route, comm_lib)
+        out.update({
             "postings_scanned_GBps": round(post_total * K / dt / 1e9, 2),
             "collective_library": dict(zip(("nccl_version", "path"), comm_lib)),
             "fresh_batch_latency_ms": None if kernel_ms_fresh != kernel_ms_fresh else round(kernel_ms_fresh, 4),
@@ -1190,7 +1257,7 @@ def main():
             "dynamic_pruning": other,
             "cpu_baseline": cpu,
             "parity_check": parity,
-        }
+        })
         if batch_d is not None:
             comp_d = compulsory_bytes(r.df if world == 1 else r.index.docfreqs(), q_distinct, B, args.k)
             out["distinct_terms"] = {

@@ -12,12 +12,12 @@ C=/tmp/corpus
 cd $R
 ( time timeout 300 python -c "import __graft_entry__ as g; g.smoke()" ) > $O/smoke.log 2>&1
 ( time timeout 1500 python -m pytest tests -m gpu -q ) > $O/pytest_gpu.log 2>&1
-( time timeout 900 python bench.py --corpus-cache $C ) > $O/bench.log 2>&1
-( time timeout 300 python bench.py --corpus-cache $C --k 100 --no-cpu-baseline --no-phrase-legs ) > $O/bench_k100.log 2>&1
-( time timeout 300 python bench.py --corpus-cache $C --k 1000 --no-cpu-baseline --no-phrase-legs ) > $O/bench_k1000.log 2>&1
-( time SA_BENCH_FORCE_COMM=1 timeout 300 python bench.py --corpus-cache $C --no-cpu-baseline --no-pmc ) > $O/bench_comm1.log 2>&1
-( time RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_PORT=29533 SA_BENCH_FORCE_COMM=1 timeout 300 python bench.py --no-cpu-baseline --no-pmc --docs 1250000 --steps 100 ) > $O/dist1_rccl.log 2>&1
-( time timeout 300 python bench.py --no-cpu-baseline --no-pmc --no-phrase-legs --docs 1250000 --steps 100 --pipeline 8 ) > $O/rank_nocomm.log 2>&1
+( time timeout 900 python bench.py --full --corpus-cache $C ) > $O/bench.log 2>&1
+( time timeout 300 python bench.py --full --corpus-cache $C --k 100 --no-cpu-baseline --no-phrase-legs ) > $O/bench_k100.log 2>&1
+( time timeout 300 python bench.py --full --corpus-cache $C --k 1000 --no-cpu-baseline --no-phrase-legs ) > $O/bench_k1000.log 2>&1
+( time SA_BENCH_FORCE_COMM=1 timeout 300 python bench.py --full --corpus-cache $C --no-cpu-baseline --no-pmc ) > $O/bench_comm1.log 2>&1
+( time RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_PORT=29533 SA_BENCH_FORCE_COMM=1 timeout 300 python bench.py --full --no-cpu-baseline --no-pmc --docs 1250000 --steps 100 ) > $O/dist1_rccl.log 2>&1
+( time timeout 300 python bench.py --full --no-cpu-baseline --no-pmc --no-phrase-legs --docs 1250000 --steps 100 --pipeline 8 ) > $O/rank_nocomm.log 2>&1
 if [ -f searcharray_amd/libsearcharray_hip_r2.so ]; then     # (round 2's library, rebuilt from commit dfc26d0 into the tree for the A/B)
 ( time timeout 600 python scripts/ab.py --corpus-cache $C --libs searcharray_amd/libsearcharray_hip_r2.so,searcharray_amd/libsearcharray_hip.so --ks 10,100,1000 --qsets baseline,distinct ) > $O/kernel_ab.log 2>&1
 ( time timeout 300 python scripts/ab.py --docs 1250000 --steps 50 --libs searcharray_amd/libsearcharray_hip_r2.so,searcharray_amd/libsearcharray_hip.so --ks 10 --qsets baseline ) >> $O/kernel_ab.log 2>&1
@@ -31,7 +31,7 @@ cd /tmp
 # kernel stats per leg: the main leg alone (one resident batch replayed), the distinct-terms leg alone, then the whole bench
 ( timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_main -- python $R/scripts/ab.py --corpus-cache $C --ks 10 --qsets baseline --steps 12 ) > $O/prof_main.log 2>&1
 ( timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_distinct -- python $R/scripts/ab.py --corpus-cache $C --ks 10 --qsets distinct --steps 12 ) > $O/prof_distinct.log 2>&1
-( timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_bench -- python $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-pmc --corpus-cache $C ) > $O/prof_bench.log 2>&1
+( timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_bench -- python $R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-pmc --corpus-cache $C ) > $O/prof_bench.log 2>&1
 ( timeout 200 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU --kernel-trace --output-format csv -d $O/prof_sq1 -- python $R/scripts/ab.py --corpus-cache $C --ks 10 --steps 2 ) > $O/prof_sq1.log 2>&1
 ( timeout 200 rocprofv3 --pmc SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_SMEM SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS --kernel-trace --output-format csv -d $O/prof_sq2 -- python $R/scripts/ab.py --corpus-cache $C --ks 10 --steps 2 ) > $O/prof_sq2.log 2>&1
 python $R/scripts/sq_summary.py $O/prof_sq1 $O/prof_sq2 > $O/sq_summary.json

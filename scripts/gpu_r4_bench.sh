@@ -5,7 +5,7 @@ O=$R/gpurun_out
 mkdir -p $O
 export TMPDIR=/tmp
 cd $R
-( time timeout 900 python bench.py --corpus-cache /tmp/corpus ) > $O/bench_r4.log 2> $O/bench_r4.err
+( time timeout 900 python bench.py --full --corpus-cache /tmp/corpus ) > $O/bench_r4.log 2> $O/bench_r4.err
 tail -c 600 $O/bench_r4.err
 python - <<'PY'
 import json

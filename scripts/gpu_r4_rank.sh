@@ -6,8 +6,8 @@ mkdir -p $O
 export TMPDIR=/tmp
 cd $R
 A="--no-cpu-baseline --no-pmc --no-phrase-legs --docs 1250000 --steps 200 --pipeline ${PIPE:-8} --corpus-cache /tmp/corpus"
-( timeout 300 python bench.py $A ) > $O/rank_nocomm.log 2>&1
-( RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_PORT=29533 SA_BENCH_FORCE_COMM=1 timeout 300 python bench.py $A ) > $O/dist1_rccl.log 2>&1
+( timeout 300 python bench.py --full $A ) > $O/rank_nocomm.log 2>&1
+( RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_PORT=29533 SA_BENCH_FORCE_COMM=1 timeout 300 python bench.py --full $A ) > $O/dist1_rccl.log 2>&1
 python - <<'PY'
 import json
 for f in ("rank_nocomm", "dist1_rccl"):
@@ -20,7 +20,7 @@ for f in ("rank_nocomm", "dist1_rccl"):
 PY
 cd /tmp
 rm -rf $O/prof_rank
-( RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_PORT=29534 SA_BENCH_FORCE_COMM=1 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_rank -- python $R/bench.py $A ) > $O/prof_rank.log 2>&1
+( RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_PORT=29534 SA_BENCH_FORCE_COMM=1 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_rank -- python $R/bench.py --full $A ) > $O/prof_rank.log 2>&1
 find $O/prof_rank -name "*kernel_stats.csv" | head -1 | xargs cat | cut -c1-160 | head -24
 find $O -name "*.db" -delete 2>/dev/null
 find $O -type f -size +8M -delete 2>/dev/null

@@ -10,7 +10,7 @@ cd $R
 tail -3 $O/smoke.log
 ( time timeout 2400 python -m pytest tests -m gpu -q -x ) > $O/pytest_gpu.log 2>&1
 tail -5 $O/pytest_gpu.log
-( time timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 ) > $O/bench_r06.json 2> $O/bench_r06.err
+( time timeout 1200 python bench.py --full --gpus 1 --steps 20 --warmup 5 ) > $O/bench_r06.json 2> $O/bench_r06.err
 tail -c 3000 $O/bench_r06.err
 python - <<'PY'
 import json

@@ -10,7 +10,7 @@ cd $R
 rm -f $O/pipeline_sweep.jsonl
 for P in 4 6 8 12 16; do
   for S in 20 100; do
-    ( timeout 400 python bench.py --steps $S --warmup 5 --pipeline $P --no-cpu-baseline --no-pmc --no-phrase-legs --corpus-cache $C ) 2> $O/pipe.err | grep "^{" | python -c "
+    ( timeout 400 python bench.py --full --steps $S --warmup 5 --pipeline $P --no-cpu-baseline --no-pmc --no-phrase-legs --corpus-cache $C ) 2> $O/pipe.err | grep "^{" | python -c "
 import sys, json
 for l in sys.stdin:
     j = json.loads(l)

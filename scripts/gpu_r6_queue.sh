@@ -10,7 +10,7 @@ C=/tmp/corpus
 cd $R
 rm -f $O/queue_driver.jsonl
 run() {
-  python bench.py "$@" --no-cpu-baseline --no-pmc --no-phrase-legs --corpus-cache $C 2>/dev/null | grep "^{" | python -c "
+  python bench.py --full "$@" --no-cpu-baseline --no-pmc --no-phrase-legs --corpus-cache $C 2>/dev/null | grep "^{" | python -c "
 import sys, json
 for l in sys.stdin:
     j = json.loads(l)

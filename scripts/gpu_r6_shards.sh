@@ -11,7 +11,7 @@ cd $R
 rm -f $O/shard_routes.jsonl
 for D in 1250000 2500000 5000000 10000000; do
   for OPT in "stage=1" "stage=0"; do
-    ( timeout 400 python bench.py --docs $D --steps 100 --warmup 10 --pipeline 8 --no-cpu-baseline --no-pmc --no-phrase-legs --corpus-cache $C --opt $OPT ) 2> $O/shard_routes.err | grep "^{" | python -c "
+    ( timeout 400 python bench.py --full --docs $D --steps 100 --warmup 10 --pipeline 8 --no-cpu-baseline --no-pmc --no-phrase-legs --corpus-cache $C --opt $OPT ) 2> $O/shard_routes.err | grep "^{" | python -c "
 import sys, json
 for l in sys.stdin:
     j = json.loads(l)

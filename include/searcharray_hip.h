@@ -62,7 +62,6 @@ typedef struct sa_options {
     int64_t sparse;          /* 1: dynamic pruning (MaxScore), 0: exhaustive scoring; unset: the rule of sa_batch_run_shard */
     int64_t group;           /* 0: no grouped kernel (queries that share their first term are scored one by one) */
     int64_t group_loose;     /* 0: no loose groups */
-    int64_t group_side;      /* 0: ungrouped rows on the batch's own stream instead of the side stream */
     int64_t group_dense;     /* 0: the grouped kernel builds its base from postings even where a dense factor row exists */
     int64_t group_one;       /* left-over queries (too dense for a loose group, first term shared with nobody) as groups of one: 2 all (default), 1 only over a dense factor row, 0 none (per-query kernel) */
     int64_t group_min;       /* smallest group (default 2) */
@@ -74,15 +73,12 @@ typedef struct sa_options {
     int64_t term_seed;       /* 0: no starting bounds from the terms' rank tables */
     int64_t topf_slice;      /* TEST HOOK: postings per workgroup of a long list's rank-table histogram (default 65536; lists of 4 slices and more) */
     int64_t seed_scale_pct;  /* TEST HOOK: starting bounds scaled by this percentage (> 100 makes them too high: the redo path) */
-    int64_t merge_small;     /* 0: the 1024-thread merge also for k <= 64 */
     int64_t impact;          /* 0: score the TF postings, no impact stream */
     int64_t pruned_topk;     /* 0: block-level selection (no bounds) */
     int64_t no_topk;         /* timing experiments: skip the per-tile selection */
     int64_t topk_hist;       /* 0: slot bound instead of the histogram bound */
-    int64_t topk_hist_mink;  /* smallest k that takes the histogram bound */
     int64_t cand_cap;        /* TEST HOOK: candidate-list capacity per query (forces the overflow handling) */
     int64_t sparse_div;      /* pruning: a lead term has at most n_docs / this postings (default 8) */
-    int64_t sparse_lazy;     /* 0: pruning tables derived at every reset, needed or not */
     int64_t bloom_floor;     /* TEST HOOK: smallest Bloom buffer in bytes */
     int64_t sp_chunk1;       /* pruning: postings per lead work item */
     int64_t stage;           /* staged-tile route (sa_stage.hip): 1 force where eligible, 0 off; unset: on where eligible and `sparse` is unset */
@@ -92,8 +88,6 @@ typedef struct sa_options {
     int64_t stage_probe;     /* 0: the staged-tile route streams EVERY term of the batch; default: terms that cannot be essential are probed in dense rows */
     int64_t probe_div;       /* probe rows (dense factor rows the staged-tile route probes) for terms with df >= n_docs / this (default 128; 0: none) */
     int64_t dense_direct;    /* 0: sa_index_bm25_dense scores the TF postings into scratch and copies (rounds 1-5); default: one launch over the impact stream, straight into the destination */
-    int64_t batch_stream;    /* 0: batches share the index stream */
-    int64_t res_xs;          /* 0: result copies on the batches' own streams */
     int64_t dense_div;       /* dense factor rows for terms with df >= n_docs / this (default 4) */
     int64_t dir_div;         /* tile directory rows for terms with df >= n_tiles / this */
     int64_t docdir_div;      /* doc directory rows for terms with >= n_docs / this words (0: none) */

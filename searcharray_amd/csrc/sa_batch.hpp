@@ -48,6 +48,7 @@ struct sa_batch {
     std::vector<u32> perm;          // device row r holds caller query perm[r] (results: caller order)
     u32* d_seed = nullptr;          // [B] (upload block, zeroed by the host) the queries' starting bounds, raised by sa_k_make_bounds
     bool seed_on = false;           // the current query set has them (non-negative weights, k1 >= 0, 0 <= b <= 1, rank tables built)
+    bool weights_ok = false;        // the current query set's weights are finite and >= 0, k1 >= 0, 0 <= b <= 1 (sa_batch_fill)
     u64 host_ns[4] = {0, 0, 0, 0};  // sa_batch_host_times
     std::vector<float> step_idf;    // sa_batch_step: the query set's weights, gathered from the index's idf table
     // Everything a NEW set of queries changes on the device is one contiguous UPLOAD BLOCK (d_up) with a
@@ -107,8 +108,7 @@ struct sa_batch {
     u32 surv_cap = 0;
     u64 sparse_p1_total = 0, sparse_limit2 = 0, sparse_p2_max = 0;
     u32 sparse_chunk1 = SA_SP_CHUNK_LEAD;
-    bool sparse_ok = false;         // tables built and the scoring formula admits the idf bound
-    bool sparse_lazy = false;       // the pruning tables of the current query set have not been derived (sa_batch_fill_prune_tables on demand)
+    bool sparse_ok = false;         // the current query set's tables are in the upload image (sa_batch_fill_prune_tables)
     u32* d_overflow = nullptr;      // set by the merge kernel when a candidate list ran over (checked at fetch); behind d_final
     u64* d_local = nullptr;         // [B][k] per-shard result
     u64* d_gather = nullptr;        // [2][nranks][B][k] (multi-GPU, double-buffered like d_xlocal)
@@ -140,14 +140,8 @@ struct sa_batch {
     bool stage_ok = false;          // the current query set has a plan (sa_stage_plan)
     bool last_route_stage = false;  // the last run took the staged-tile route
     bool bounds_valid = false;      // d_bounds / d_qbase / d_qbase_imp hold the current query set's slice table (the staged route does not need it)
-    u32 st_U = 0, st_NS = 0;        // distinct terms of the query set; the first st_NS are staged, the others probed in their probe rows
-    u32 st_docs = 0;                // docs per stage tile
-    float st_cand_per_doc = 0.f;    // candidates (postings of essential terms) per document the plan expects, all queries together
-    u32 st_imp_bytes = 0;           // bytes of the stream from st_cell_base to the end of the set's last term
-    u64 st_cell_base = 0;           // smallest impact-stream cell of the set's terms (the kernel's 32-bit offsets count from it)
-    u32 st_tmax = 4;                // kernel instantiation: 4 or 8 terms per query
-    std::shared_ptr<sa_stagedir> st_dir;
-    std::vector<sa_stage_slice> st_slices;   // the current set's plan, slice by slice (empty: none); the st_* fields above repeat slice 0
+    std::shared_ptr<sa_stagedir> st_dir;     // the stage directory of the set's first slice (the next plan reuses it)
+    std::vector<sa_stage_slice> st_slices;   // the current set's plan, slice by slice (empty: none)
     sa_stage_scratch st_work;       // the plan's working arrays (kept between plans: a plan allocates nothing)
     char* d_st = nullptr;           // the plan's region of the upload block (sa_stage_bind carves it)
     size_t st_bytes = 0;
@@ -174,8 +168,18 @@ int sa_comm_allreduce_max_u32(sa_index* ix, u32* d_val, hipStream_t st);
 
 // tile scoring + pruned selection of a phrase batch on stream st (sa_phrase_batch.hip)
 int sa_launch_phrase_tiles(sa_batch* bt, hipStream_t st);
-// shared by the two batch kinds (sa_bm25.hip)
-int sa_batch_alloc_topk(sa_batch* bt, u32 n_tiles, u32 waves);
+// The shard run of a batch -- stage 1 (tile scoring + per-tile top-k) and stage 2 (per-shard merge into shard_out) on the batch's
+// stream: sa_batch_run_bm25 (sa_batch.hip) or sa_phrase_batch_run_shard (sa_phrase_batch.hip).  `deferred`: an overflowing
+// candidate list is flagged in overflow_cell (else d_overflow) instead of checked on the host; `unpruned`: the redo of a
+// flagged run.  A phrase run takes neither.
+typedef int (*sa_shard_run)(sa_batch* bt, u64* shard_out, bool deferred, bool unpruned, u32* overflow_cell);
+int sa_phrase_batch_run_shard(sa_batch* bt, u64* shard_out, bool deferred, bool unpruned, u32* overflow_cell);
+// shared by the two batch kinds (sa_batch.hip): buffers sized for n_tiles tiles of `waves` waves, candidate lists of at least
+// min_cap keys; the run-state clear, the host overflow check and the per-shard merge of a run
+int sa_batch_alloc_topk(sa_batch* bt, u32 n_tiles, u32 waves, u64 min_cap);
+void sa_batch_clear_state(sa_batch* bt, bool pruned, bool bloom);
+int sa_batch_overflowed(sa_batch* bt, bool* over);
+void sa_batch_merge_shard(sa_batch* bt, u64* shard_out, u32 n_tiles, bool pruned, bool hist, u32* overflow, const u32* seed);
 // the upload block (sa_batch.hpp: d_up / h_up): allocate, take the next host image, enqueue its copy
 int sa_batch_alloc_upload(sa_batch* bt, size_t bytes);
 // host time of the step's parts, cumulative nanoseconds (sa_batch_host_times): [0] sa_batch_fill up to the upload (grouping, pruning
@@ -194,3 +198,15 @@ int sa_stage_plan(sa_batch* bt, char* img, const u32* row_terms, const float* ro
 int sa_launch_stage(sa_batch* bt, const struct Bm25Params& p, hipStream_t st);
 // dynamic pruning: lead-term candidates, routing, remaining essential candidates (sa_sparse.hip)
 int sa_launch_sparse(sa_batch* bt, hipStream_t st);
+// the impact stream and launchers of sa_bm25.hip the batch code calls
+std::shared_ptr<sa_impacts> sa_impacts_get(sa_index* ix, float k1, float b, const sa_options_t& o);
+void sa_impacts_ensure_topf(sa_index* ix, sa_impacts* im);
+int sa_launch_make_sattab(sa_index* ix, float* d_tab, u32* tab_w_out, float k1, float b, hipStream_t st);
+int sa_launch_make_bounds(sa_index* ix, const u32* d_terms, u32 BT, u32* d_bounds, u64* d_qbase, hipStream_t st,
+                          u64* d_qbase_imp = nullptr, const float* d_topf = nullptr, const float* d_idf = nullptr, u32 T = 1,
+                          u32 k = 1, u32* d_seed = nullptr, float seed_scale = 1.f);
+void sa_launch_run_reset(u32* slots, u64 words, u64* bloom, u64 n8, u32* one_more, hipStream_t st);
+void sa_launch_topk_merge(u32 B, hipStream_t st, u64* cand, u32 n_cand_max, u32 k, u64* out, const u32* out_row, u32 rank_stride,
+                          const u32* cnt, const u32* slots, const u32* gthr, u32* overflow, u32* clr_state, u32 clr_B, u32 clr_hist,
+                          u32* clr_one, u32 gather_stride, u32* xflag, const u32* seed);
+void sa_launch_regroup(const u64* gathered, u32 nranks, u32 B, u32 k, u32 extra, u64* out, u32* xflag, hipStream_t st);

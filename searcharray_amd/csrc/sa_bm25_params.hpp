@@ -5,6 +5,21 @@
 
 struct alignas(16) sa_u64x2 { u64 x, y; };
 
+// saturation table (sa_k_make_sattab, sa_bm25.hip): term frequencies 1 .. SA_SAT_NTF x doc lengths below at most SA_SAT_WMAX
+#define SA_SAT_NTF 8
+#define SA_SAT_WMAX 128
+// grouped kernel (sa_k_bm25_group_tiles, sa_bm25.hip) and the grouping of a batch's rows (sa_batch.hip)
+#define SA_GRP_MAXQ 16      // queries per table pass of a group item
+#define SA_GRP_ITEM_ROUNDS 16    // items of 32 queries (two table passes) from this many rounds of 4096 one-pass items on; option group_item
+#define SA_GRP_LOOSE_POSTINGS 400   // loose groups: expected postings of a query per tile, all terms together (SA_LOOSE_POSTINGS).  Round 3,
+                                    // distinct-terms batch, 10 M docs: 64 / 96 / 128 / 192 / 256 / 384 / 512 -> 0.82 / 0.74 / 0.74 / 0.73 / 0.75 /
+                                    // 0.80 / 0.81 ms at k = 10, hence 128.  Round 4, with the starting bounds (the per-query kernel AND the
+                                    // overlay both start with a bound): 32 / 64 / 96 / 128 / 192 / 256 / 320 / 400 / 500 / 640 / 900 / all ->
+                                    // 1.00 / 0.80 / 0.62 / 0.54 / 0.50 / 0.47 / 0.457 / 0.459 / 0.468 / 0.476 / 0.483 / 0.485 ms at k = 10;
+                                    // k = 1000: 128 / 320 / 400 / 500 / 640 -> 0.89 / 0.84 / 0.81 / 0.77 / 0.81
+// keys of one query the merge (sa_k_topk_merge) holds in LDS
+#define SA_MERGE_LIST 2048
+
 // Impact stream layout (sa_impacts, sa_index.hpp): first cell of term `term` whose TF postings start at tf_base
 // (4 cells of slack per term: a term's last posting is followed by at least one whole, 16-byte-aligned pair
 //  of sentinels before the next term starts -- the pair every load past a slice's term is clamped to)
@@ -58,3 +73,10 @@ struct Bm25Params {
     float* dense_out;      // [B][n_docs] or null
     u64* cand;             // [B][n_tiles][k] composite keys (global doc ids) or null
 };
+
+// host launchers of the BM25 kernels (sa_bm25.hip), called by the batch code (sa_batch.hip)
+void sa_fill_params(const sa_index* ix, Bm25Params& p);
+u32 sa_tile_waves(u32 tile_docs);
+int sa_launch_bm25(sa_index* ix, const Bm25Params& p, hipStream_t st);                // per-query tile kernel (p.qlist: rows)
+int sa_launch_bm25_list(sa_index* ix, const Bm25Params& p, hipStream_t st);           // ... over the device's query list
+int sa_launch_bm25_groups(sa_index* ix, const struct sa_batch* bt, const Bm25Params& p, u32 tile0, hipStream_t st);

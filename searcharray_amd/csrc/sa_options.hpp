@@ -14,10 +14,9 @@
 // X(field)  -- order = order of the fields in sa_options_t
 #define SA_OPTION_LIST(X)                                                                                                          \
     /* ---- BM25 top-k batches (sa_bm25.hip, sa_sparse.hip) */                                                                     \
-    X(sparse)          /* 1: dynamic pruning (MaxScore), 0: exhaustive scoring; unset: the rule of sa_batch_run_shard */           \
+    X(sparse)          /* 1: dynamic pruning (MaxScore), 0: exhaustive scoring; unset: the route rule (sa_batch_plan) */          \
     X(group)           /* 0: no grouped kernel (queries that share their first term are scored one by one) */                       \
     X(group_loose)     /* 0: no loose groups */                                                                                    \
-    X(group_side)      /* 0: ungrouped rows on the batch's own stream instead of the side stream */                                \
     X(group_dense)     /* 0: the grouped kernel builds its base from postings even where a dense factor row exists */              \
     X(group_one)       /* left-over queries (too dense for a loose group, first term shared with nobody) as groups of one: 2 all (default), 1 only over a dense factor row, 0 none (per-query kernel) */ \
     X(group_min)       /* smallest group (default 2) */                                                                            \
@@ -29,15 +28,12 @@
     X(term_seed)       /* 0: no starting bounds from the terms' rank tables */                                                     \
     X(topf_slice)      /* TEST HOOK: postings per workgroup of a long list's rank-table histogram (default 65536; lists of 4 slices and more) */ \
     X(seed_scale_pct)  /* TEST HOOK: starting bounds scaled by this percentage (> 100 makes them too high: the redo path) */       \
-    X(merge_small)     /* 0: the 1024-thread merge also for k <= 64 */                                                             \
     X(impact)          /* 0: score the TF postings, no impact stream */                                                            \
     X(pruned_topk)     /* 0: block-level selection (no bounds) */                                                                  \
     X(no_topk)         /* timing experiments: skip the per-tile selection */                                                       \
     X(topk_hist)       /* 0: slot bound instead of the histogram bound */                                                          \
-    X(topk_hist_mink)  /* smallest k that takes the histogram bound */                                                             \
     X(cand_cap)        /* TEST HOOK: candidate-list capacity per query (forces the overflow handling) */                           \
     X(sparse_div)      /* pruning: a lead term has at most n_docs / this postings (default 8) */                                   \
-    X(sparse_lazy)     /* 0: pruning tables derived at every reset, needed or not */                                               \
     X(bloom_floor)     /* TEST HOOK: smallest Bloom buffer in bytes */                                                             \
     X(sp_chunk1)       /* pruning: postings per lead work item */                                                                  \
     X(stage)           /* staged-tile route (sa_stage.hip): 1 force where eligible, 0 off; unset: on where eligible and `sparse` is unset */ \
@@ -47,8 +43,6 @@
     X(stage_probe)     /* 0: the staged-tile route streams EVERY term of the batch; default: terms that cannot be essential are probed in dense rows */ \
     X(probe_div)       /* probe rows (dense factor rows the staged-tile route probes) for terms with df >= n_docs / this (default 128; 0: none) */ \
     X(dense_direct)    /* 0: sa_index_bm25_dense scores the TF postings into scratch and copies (rounds 1-5); default: one launch over the impact stream, straight into the destination */ \
-    X(batch_stream)    /* 0: batches share the index stream */                                                                     \
-    X(res_xs)          /* 0: result copies on the batches' own streams */                                                          \
     /* ---- index creation (sa_index.hip, sa_bm25.hip) */                                                                          \
     X(dense_div)       /* dense factor rows for terms with df >= n_docs / this (default 4) */                                      \
     X(dir_div)         /* tile directory rows for terms with df >= n_tiles / this */                                               \

@@ -362,6 +362,28 @@ int sa_launch_phrase_tiles(sa_batch* bt, hipStream_t st) {
     return SA_OK;
 }
 
+// The shard run of a phrase batch (sa_shard_run, sa_batch.hpp): tile scoring with the pruned selection, then the per-shard
+// merge.  A candidate list that ran over is an error: there is no unpruned phrase route to fall back to.
+int sa_phrase_batch_run_shard(sa_batch* bt, u64* shard_out, bool /*deferred*/, bool /*unpruned*/, u32* /*overflow_cell*/) {
+    sa_batch_clear_state(bt, true, false);
+    const u32 slot = bt->ev_n % SA_EVENT_RING;
+    SA_HIP(hipEventRecord(bt->ev0[slot], bt->st));
+    if (bt->ix->avg_doc_len != 0.f && bt->pn_tiles > 0) SA_TRY(sa_launch_phrase_tiles(bt, bt->st));
+    else SA_HIP(hipMemsetAsync(bt->d_cand, 0, (size_t)bt->B * bt->cand_cap * sizeof(u64), bt->st));
+    SA_HIP(hipEventRecord(bt->ev1[slot], bt->st));
+    bt->ev_n++;
+    if (bt->cap_limited && bt->pn_tiles > 0) {
+        bool over = false;
+        SA_TRY(sa_batch_overflowed(bt, &over));
+        if (over) {
+            sa_set_error("phrase batch: candidate list overflow (k too large for this many matching tiles)");
+            return SA_ERR_UNSUPPORTED;
+        }
+    }
+    sa_batch_merge_shard(bt, shard_out, bt->pn_tiles, true, false, nullptr, nullptr);
+    return SA_OK;
+}
+
 extern "C" int sa_phrase_batch_create(sa_index_t* ix, const uint32_t* terms, const int32_t* n_terms, const float* idf,
                                       int n_phrases, int max_terms, int k, float k1, float b, sa_batch_t** out) {
     return sa_phrase_batch_create_ex(ix, terms, n_terms, nullptr, idf, n_phrases, max_terms, k, k1, b, out);
@@ -486,7 +508,7 @@ extern "C" int sa_phrase_batch_create_ex(sa_index_t* ix, const uint32_t* terms, 
         SA_HIP(hipMalloc(&bt->d_wlen, (size_t)B * T * sizeof(u32)));
         // (every wave of a ranking unit appends at most k keys: 4 waves per tile of the tile route -- and per block of 512 documents
         //  of the slop phrases that rank inside the span kernel, sa_k_span_doc_fused_multi: 4 such blocks per 2048-doc tile)
-        SA_TRY(sa_batch_alloc_topk(bt, bt->pn_tiles, (SA_PTHREADS / SA_WAVE) * (bt->ptile / 512u)));
+        SA_TRY(sa_batch_alloc_topk(bt, bt->pn_tiles, (SA_PTHREADS / SA_WAVE) * (bt->ptile / 512u), 0));
         return SA_OK;
     };
     int rc = alloc();

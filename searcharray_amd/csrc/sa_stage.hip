@@ -529,9 +529,7 @@ int sa_stage_plan(sa_batch* bt, char* img, const u32* row_terms, const float* ro
             return SA_OK;
         }
     }
-    const sa_stage_slice& f = bt->st_slices[0];
-    bt->st_U = f.U; bt->st_NS = f.NS; bt->st_docs = f.docs; bt->st_tmax = f.tmax; bt->st_cand_per_doc = f.cand_per_doc;
-    bt->st_cell_base = f.cell_base; bt->st_imp_bytes = f.imp_bytes; bt->st_dir = f.dir;
+    bt->st_dir = bt->st_slices[0].dir;
     bt->stage_ok = true;
     return SA_OK;
 }

@@ -511,6 +511,47 @@ def test_dynamic_pruning_default_policy(api, monkeypatch):
         bt.close()
 
 
+@pytest.fixture(scope="module")
+def route_corpus(api):
+    n_docs, vocab = 60000, 3000
+    t, d, p, lens = synth.corpus_triples(n_docs, vocab, 12, seed=5)
+    words, wt = rz.encode_sorted(t, d, p)
+    dev = DeviceIndex(words, rz.term_offsets(wt, vocab), lens, tile_docs=1024, api=api)
+    orc = O.OracleIndex.from_triples(t, d, p, n_docs, doc_lens=lens)
+    queries = np.asarray([[0, 40, 700, 2500], [2900, 1, 3, 1500], [2999, 2998, 0, 1]] + [[i, 50 + i, 900 + i, 2000 + i] for i in range(6)])
+    return dev, orc, queries
+
+
+# (groups, grouped queries, of them with a shared first term, queries left to the per-query kernel)
+_GROUPED = (6, 9, 2, 0)
+
+
+@pytest.mark.parametrize("opts, routes, groups", [
+    ({}, ("staged", "staged", "staged"), _GROUPED),
+    ({"stage": 0}, ("exhaustive", "exhaustive", "exhaustive"), _GROUPED),
+    ({"stage": 1}, ("staged", "staged", "staged"), _GROUPED),
+    ({"sparse": 0}, ("exhaustive", "exhaustive", "exhaustive"), _GROUPED),
+    ({"sparse": 1}, ("pruned", "pruned", "pruned"), _GROUPED),
+    ({"stage": 0, "sparse": 1}, ("pruned", "pruned", "pruned"), _GROUPED),
+    ({"impact": 0}, ("pruned", "exhaustive", "exhaustive"), (2, 5, 2, 4)),     # (no groups of one without the impact stream)
+    ({"group": 0}, ("staged", "staged", "staged"), (0, 0, 0, 9)),
+], ids=["unset", "stage0", "stage1", "sparse0", "sparse1", "stage0_sparse1", "impact0", "group0"])
+def test_route_table(route_corpus, opts, routes, groups):
+    """The route rule as a table: the routes of one query set on a 60 000-doc shard for k = 1, 8, 40 (both sides of 8192 docs
+    per requested result and of k = 32) under the route-selecting options, the group layout, and the oracle's top-k in every cell."""
+    dev, orc, queries = route_corpus
+    for k, route in zip((1, 8, 40), routes):
+        bt = dev.batch(queries, k=k, opts=opts)
+        bt.stats(True)
+        _check_batch(bt, orc, queries, k)
+        _, sparse_queries = bt.stats(False)
+        gi = bt.group_info()
+        assert bt.last_route() == route, (opts, k)
+        assert (gi["groups"], gi["grouped_queries"], gi["shared_first_term"], gi["per_query_kernel"]) == groups, (opts, k)
+        assert (sparse_queries > 0) == (route == "pruned"), (opts, k)
+        bt.close()
+
+
 def test_threaded_batches_share_impact_streams(api, monkeypatch):
     """Batches with different (k1, b) created, run and closed from several threads on one index (the C ABI
     serialises calls per index handle; an impact stream lives as long as a batch uses it, the index caches only

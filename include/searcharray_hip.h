@@ -379,6 +379,41 @@ int sa_batch_merge_gathered(sa_batch_t* batch, const void* gathered_keys_device,
 int sa_index_set_idf_table(sa_index_t* ix, const float* idf_per_term, uint32_t n_terms);
 int sa_batch_step(sa_batch_t* batch, const uint32_t* terms);
 
+/* ---- Part 2b: DOCUMENT FILTERS (csrc/sa_filter.hip) -- ranking inside a subset of the index, as a Solr `fq` does.  A filter is an immutable
+ * bitmap over the documents of ONE index (shard-local, one bit per doc, with a count per 1024 docs so that kernels skip tiles that hold
+ * nothing).  A BM25 batch that holds one (sa_batch_set_filter) returns, per query, exactly the top-k of the unfiltered scores with the
+ * scores of the non-eligible documents set to 0: the same scores bit for bit -- idf, average doc length and corpus size stay those of the
+ * WHOLE index, a filter leaves scoring alone -- in the same order; unused slots as always.  This is NOT the reference's slice semantics
+ * (arr[rows].score(...) recomputes docfreq inside the slice, postings.py:604-617).  One filter per batch, shared by its queries.
+ * A filter is built on the index stream and complete when its call returns.  The handle and the batches that hold the filter share it by
+ * reference count: sa_filter_destroy while a batch still uses it is safe. */
+typedef struct sa_filter sa_filter_t;
+#define SA_FILTER_AND 0
+#define SA_FILTER_OR 1
+#define SA_FILTER_ANDNOT 2
+/* doc_ids: GLOBAL ids (the index's doc_base is subtracted; ids outside the shard are ignored), any order, duplicates allowed */
+int sa_filter_create_from_rows(sa_index_t* index, const uint64_t* doc_ids, uint64_t n, sa_filter_t** out);
+/* mask: one byte per (local) document, non-zero = eligible; n_docs must be the index's */
+int sa_filter_create_from_mask(sa_index_t* index, const uint8_t* mask, uint64_t n_docs, sa_filter_t** out);
+/* the documents that contain `term` (from its TF postings, on the device); an unknown term gives the empty filter */
+int sa_filter_create_from_term(sa_index_t* index, uint32_t term, sa_filter_t** out);
+/* a op b (SA_FILTER_AND / _OR / _ANDNOT: a and not b) of two filters of the same index; the complement (bits behind n_docs stay 0) */
+int sa_filter_combine(sa_filter_t* a, sa_filter_t* b, int op, sa_filter_t** out);
+int sa_filter_not(sa_filter_t* a, sa_filter_t** out);
+/* eligible documents; the filter as one byte (0 / 1) per document: mask_out[n_docs] */
+int sa_filter_count(sa_filter_t* filter, uint64_t* n_out);
+int sa_filter_fetch(sa_filter_t* filter, uint8_t* mask_out);
+int sa_filter_destroy(sa_filter_t* filter);
+/* The batch ranks inside `filter` from its next run on (NULL: the whole index again), including runs of the query set already loaded:
+ * the set is prepared again for the new state (a filtered run never starts from the rank-table bounds of the whole corpus, and
+ * sa_batch_seeds reports 0 for it).  Legal whenever sa_batch_reset is: runs in flight are ordered on the batch's stream, and a run
+ * whose results have not been fetched keeps the filter it ran with.  The filter persists across sa_batch_reset / sa_batch_step like the
+ * batch's options.  Routes: the staged-tile route, the grouped overlay and the per-query tile kernels honour the filter; dynamic
+ * pruning does not, and the route rule never picks it for a filtered batch (option sparse = 1 with a filter: the exhaustive kernels,
+ * sa_batch_last_route says 0).  A filter of another index -> SA_ERR_ARG.  Phrase batches and the timing option no_topk do not take
+ * a filter (SA_ERR_UNSUPPORTED). */
+int sa_batch_set_filter(sa_batch_t* batch, sa_filter_t* filter);
+
 /* ---- Part 2c: a query-set QUEUE (csrc/sa_queue.hip).  A ring of `depth` batches of the same shape behind one handle, fed by a WORKER
  * THREAD of the library: sa_queue_submit copies a set of B x T term ids (weights come from the index's idf table, sa_index_set_idf_table,
  * as for sa_batch_step) and returns a ticket -- it blocks only while `depth` tickets are outstanding; the worker runs sa_batch_step for
@@ -537,6 +572,15 @@ int sa_sharded_batch_run(sa_sharded_batch_t* batch, int sync);
 int sa_sharded_batch_set_options(sa_sharded_batch_t* batch, const sa_options_t* opts);
 int sa_sharded_batch_fetch(sa_sharded_batch_t* batch, float* scores_out, uint64_t* docs_out);
 int sa_sharded_batch_destroy(sa_sharded_batch_t* batch);
+/* document filters (Part 2b) over all shards: GLOBAL doc ids / one byte per document of the whole corpus, fanned out by the shard bounds
+ * (sa_sharded_info) to one filter per shard, each built on its shard's thread */
+typedef struct sa_sharded_filter sa_sharded_filter_t;
+int sa_sharded_filter_create_from_rows(sa_sharded_t* sh, const uint64_t* doc_ids, uint64_t n, sa_sharded_filter_t** out);
+int sa_sharded_filter_create_from_mask(sa_sharded_t* sh, const uint8_t* mask, uint64_t n_docs, sa_sharded_filter_t** out);
+int sa_sharded_filter_count(sa_sharded_filter_t* filter, uint64_t* n_out);
+int sa_sharded_filter_destroy(sa_sharded_filter_t* filter);
+/* sa_batch_set_filter on every shard's batch (NULL clears) */
+int sa_sharded_batch_set_filter(sa_sharded_batch_t* batch, sa_sharded_filter_t* filter);
 
 /* ------------------------------------------------------------------------------------- */
 /* Part 4 -- dense vectors on the device: the combine step of Solr-style multi-field queries */

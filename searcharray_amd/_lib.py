@@ -140,6 +140,21 @@ PROTOTYPES = {
     "sa_sharded_batch_set_options": (c_int, [c_void_p, c_void_p]),
     "sa_sharded_batch_fetch": (c_int, [c_void_p, f32p, u64p]),
     "sa_sharded_batch_destroy": (c_int, [c_void_p]),
+    # Part 2b: document filters
+    "sa_filter_create_from_rows": (c_int, [c_void_p, u64p, c_uint64, POINTER(c_void_p)]),
+    "sa_filter_create_from_mask": (c_int, [c_void_p, c_void_p, c_uint64, POINTER(c_void_p)]),
+    "sa_filter_create_from_term": (c_int, [c_void_p, c_uint32, POINTER(c_void_p)]),
+    "sa_filter_combine": (c_int, [c_void_p, c_void_p, c_int, POINTER(c_void_p)]),
+    "sa_filter_not": (c_int, [c_void_p, POINTER(c_void_p)]),
+    "sa_filter_count": (c_int, [c_void_p, u64p]),
+    "sa_filter_fetch": (c_int, [c_void_p, c_void_p]),
+    "sa_filter_destroy": (c_int, [c_void_p]),
+    "sa_batch_set_filter": (c_int, [c_void_p, c_void_p]),
+    "sa_sharded_filter_create_from_rows": (c_int, [c_void_p, u64p, c_uint64, POINTER(c_void_p)]),
+    "sa_sharded_filter_create_from_mask": (c_int, [c_void_p, c_void_p, c_uint64, POINTER(c_void_p)]),
+    "sa_sharded_filter_count": (c_int, [c_void_p, u64p]),
+    "sa_sharded_filter_destroy": (c_int, [c_void_p]),
+    "sa_sharded_batch_set_filter": (c_int, [c_void_p, c_void_p]),
     "sa_index_select_rows": (c_int, [c_void_p, u64p, c_uint64]),
     "sa_host_alloc": (c_int, [c_uint64, POINTER(c_void_p)]),
     "sa_host_free": (c_int, [c_void_p]),

@@ -38,6 +38,10 @@ static sa_plan sa_batch_plan(const sa_batch* bt, bool deferred, bool unpruned) {
     const sa_index* ix = bt->ix;
     const sa_options_t& o = bt->opts;
     sa_plan pl;
+    // A batch with a document filter (sa_batch_set_filter) only ever takes a route that honours it: the staged-tile route, the grouped
+    // overlay or the per-query tile kernels.  Dynamic pruning does not look at the filter, so the rule keeps a filtered batch off it
+    // whatever the options say; and it starts without the rank-table bounds, which hold for the whole corpus only.
+    const bool filtered = bt->filter != nullptr;
     // (the grouped kernel and the starting bounds need non-negative scores: the sign bit is a mark)
     pl.group = sa_opt(o.group, 1) != 0 && bt->weights_ok && sa_grouped_tiles(ix->tile_docs);
     pl.seed_wanted = bt->weights_ok && bt->impacts && bt->k <= 1024u && sa_opt(o.term_seed, 1) != 0 && sa_opt(o.sparse, -1) != 1;
@@ -68,7 +72,8 @@ static sa_plan sa_batch_plan(const sa_batch* bt, bool deferred, bool unpruned) {
     // ... and so do the loose groups on batches WITHOUT shared terms (256 x 4 pairwise-distinct terms of ranks 1 .. 1024,
     // all of them frequent: 0.62 ms exhaustive vs 1.68 ms pruned at k = 10): the exhaustive path is the default whenever
     // at least half of the batch's queries are in groups of either sort.
-    const bool grouped = bt->n_groups && impact_route && sa_opt(o.group, 1) != 0;
+    // (the overlay's filtered instantiations exist for 1024- and 2048-doc tiles)
+    const bool grouped = bt->n_groups && impact_route && sa_opt(o.group, 1) != 0 && !(filtered && ix->tile_docs > 2048u);
     // Unset, `sparse` follows the measurements: pruning pays while the shard holds many docs per requested
     // result (10 M docs: 2.2x at k = 10, 1.9x at k = 100, but the exhaustive kernel is 1.2x faster at k = 1000;
     // 1.25 M docs, k = 1000: exhaustive 1.8x faster) -- on from 32768 docs per result (8192 since round 6, below).  sparse = 1 / 0 force it.
@@ -80,12 +85,12 @@ static sa_plan sa_batch_plan(const sa_batch* bt, bool deferred, bool unpruned) {
     // Round 6: the staged-tile route (sa_stage.hip) takes every query set it has a plan for -- distinct terms staged in LDS once
     // per tile, the queries answered from there; it needs the histogram bound and the impact stream like the grouped kernel
     const bool stage = bt->stage_ok && pl.stage_wanted && hist_possible && pl.imp && !no_topk && ix->avg_doc_len != 0.f;
-    const bool sparse = !stage && sparse_wanted && hist_possible && ix->tile_docs <= 8192 && ix->avg_doc_len != 0.f && ix->n_tiles > 0;
+    const bool sparse = !stage && !filtered && sparse_wanted && hist_possible && ix->tile_docs <= 8192 && ix->avg_doc_len != 0.f && ix->n_tiles > 0;
     // (a run that checks overflow on the host keeps the slot bound up to k = 32)
     pl.hist = hist_possible && (sparse || stage || deferred || bt->k > 32);
     pl.route = stage ? SA_ROUTE_STAGED : sparse ? SA_ROUTE_PRUNED : grouped && pl.hist ? SA_ROUTE_GROUPED : SA_ROUTE_TILES;
     // the bounds the queries start with (exhaustive kernels only: the pruning path derives its own from the lead terms)
-    pl.seed = pl.hist && !sparse && bt->seed_on && pl.imp;
+    pl.seed = pl.hist && !sparse && bt->seed_on && pl.imp && !filtered;
     // (with the histogram bound a wave appends all its survivors, so the worst case is not bounded by k)
     pl.may_overflow = pl.pruned && (bt->cap_limited || pl.hist) && ix->n_tiles > 0;
     return pl;
@@ -630,14 +635,16 @@ static int sa_batch_fill(sa_batch* bt, const uint32_t* terms, const float* idf) 
     if (!h_grp.empty()) memcpy(h_grpd, h_grp.data(), h_grp.size() * sizeof(u32));     // (at most B groups)
     memset(at(bt->d_seed), 0, (size_t)B * sizeof(u32));
     if (pl.seed_wanted) sa_impacts_ensure_topf(ix, bt->impacts.get());
-    bt->seed_on = pl.seed_wanted && bt->impacts->d_topf;
+    const bool tables = pl.seed_wanted && bt->impacts->d_topf;   // the rank tables and the terms' largest factors exist
+    bt->seed_on = tables && !bt->filter;                        // (a filtered set starts from 0: the tables' bounds count docs the filter may exclude)
     // the staged-tile route's plan (sa_stage.hip): distinct terms, per-query bound tables and the starting bounds, formed on the
     // host into the same upload.  A set that has one does not need the slice table: sa_k_make_bounds is left out of the step and
     // only runs if the run takes another route after all (sa_batch_ensure_bounds)
     bt->stage_ok = false;
     bt->st_dir.reset();
     bt->st_slices.clear();
-    if (bt->seed_on && pl.stage_wanted) SA_TRY(sa_stage_plan(bt, img, h_terms, h_idf));
+    // (a filtered set is planned with zero starting bounds: every term staged, none probed)
+    if (tables && pl.stage_wanted) SA_TRY(sa_stage_plan(bt, img, h_terms, h_idf));
     // the pruning tables: now, if the run will prune (the route rule, now that the groups and the staged plan are known); else on demand
     if (sa_batch_plan(bt, true, false).route == SA_ROUTE_PRUNED) sa_batch_fill_prune_tables(bt, img);
     else { bt->sparse_ok = false; bt->bloom_bytes = 0; bt->sparse_p1_total = 0; bt->sparse_p2_max = 0; }
@@ -696,6 +703,43 @@ extern "C" int sa_batch_reset(sa_batch_t* bt, const uint32_t* terms, const float
         SA_TRY(sa_batch_redo_if_flagged(bt));                   // (a flagged run is redone while the tables still hold ITS query set)
     }
     return sa_batch_fill(bt, terms, idf);
+}
+
+// Part 2b: the batch ranks inside `f` from its next run on (null: the whole index).  The loaded query set is prepared again -- its
+// starting bounds, groups and staged plan belong to the filter state they were made for.
+extern "C" int sa_batch_set_filter(sa_batch_t* bt, sa_filter_t* f) {
+    SA_ARG(bt && bt->ix, "null batch");
+    if (bt->kind != 0) { sa_set_error("sa_batch_set_filter: phrase batches do not take a document filter"); return SA_ERR_UNSUPPORTED; }
+    SA_ARG(!f || f->d, "null filter");
+    sa_index* ix = bt->ix;
+    SA_ARG(!f || (f->d->ix == ix && f->d->n_docs == ix->n_docs), "the filter was built for another index");
+    std::lock_guard<std::mutex> g(ix->mu);
+    SA_HIP(hipSetDevice(ix->device));
+    if (f && sa_opt(bt->opts.no_topk, 0) != 0) { sa_set_error("sa_batch_set_filter: not with the timing option no_topk"); return SA_ERR_UNSUPPORTED; }
+    if (!f && !bt->filter) return SA_OK;
+    // (as in sa_batch_reset: an unfetched run that was flagged is redone first -- with the filter and the tables it ran with)
+    if (bt->res_pending && bt->unfetched) {
+        SA_HIP(hipEventSynchronize(bt->ev_res));
+        SA_TRY(sa_batch_redo_if_flagged(bt));
+    }
+    if (bt->filter) SA_HIP(hipStreamSynchronize(bt->st));       // (runs in flight read the bitmap this call may release)
+    bt->filter = f ? f->d : nullptr;
+    if (sa_opt(bt->opts.trace, 0)) fprintf(stderr, "sa_batch_set_filter: %llu of %llu docs eligible\n", f ? (unsigned long long)f->d->count : (unsigned long long)ix->n_docs, (unsigned long long)ix->n_docs);
+    // the loaded set, back in caller order, from the upload image it was filled into (device-row order + the row order; the image's
+    // copy to the device has left the host buffer when its event has fired; the fill below writes the OTHER image)
+    const u32 last = (bt->up_n - 1u) & 1u;
+    SA_HIP(hipEventSynchronize(bt->ev_up[last]));
+    const char* img = bt->h_up[last];
+    const u32* r_terms = (const u32*)(img + ((const char*)bt->d_terms - bt->d_up));
+    const float* r_idf = (const float*)(img + ((const char*)bt->d_idf - bt->d_up));
+    const size_t T = bt->T;
+    std::vector<u32> terms((size_t)bt->B * T);
+    std::vector<float> idf((size_t)bt->B * T);
+    for (u32 r = 0; r < bt->B; r++) {
+        memcpy(&terms[(size_t)bt->perm[r] * T], &r_terms[(size_t)r * T], T * sizeof(u32));
+        memcpy(&idf[(size_t)bt->perm[r] * T], &r_idf[(size_t)r * T], T * sizeof(float));
+    }
+    return sa_batch_fill(bt, terms.data(), idf.data());
 }
 
 extern "C" int sa_index_set_idf_table(sa_index_t* ix, const float* idf_per_term, uint32_t n_terms) {
@@ -788,6 +832,7 @@ static Bm25Params sa_batch_params(const sa_batch* bt, const sa_plan& pl) {
     p.gthr = pl.hist ? bt->d_gthr : nullptr;
     p.seed = pl.seed ? bt->d_seed : nullptr;
     p.qlist = nullptr; p.nq = bt->B;
+    if (bt->filter) { p.filt = bt->filter->d_words; p.filt_blk = bt->filter->d_blk; p.filt_nblk = bt->filter->n_blocks; }
     return p;
 }
 
@@ -804,7 +849,11 @@ static int sa_batch_launch_grouped(sa_batch* bt, const Bm25Params& p) {
     //  starting bounds 0.420; 1.25 M-doc shard: 0.096 / 0.094 / - / 0.0825 against 0.126)
     if (p.seed) warm = 0;
     if (sa_opt_is_set(bt->opts.group_warm)) warm = (u32)std::max<long long>(0, bt->opts.group_warm);
-    warm = std::min(warm, ix->n_tiles);
+    // a filtered batch warms up on the first tiles that HOLD eligible docs (the tiles in front of them are empty for every kernel):
+    // a filter that starts deep in the shard would otherwise leave the overlay without bounds, and every pair to the per-query kernel
+    u32 t0 = 0;
+    if (bt->filter) t0 = std::min<u32>(bt->filter->first_block / (ix->tile_docs / SA_FILTER_BLOCK), ix->n_tiles);
+    warm = std::min(warm, ix->n_tiles - t0);
     // The ungrouped rows (per-query kernel over all tiles) share nothing with the grouped ones -- not a
     // query, not a counter -- so they run on the side stream BESIDE the warm-up tiles and the grouped kernel
     // (a few dense queries are a small grid of long workgroups: alone on the device they took 0.28 ms of a
@@ -827,10 +876,10 @@ static int sa_batch_launch_grouped(sa_batch* bt, const Bm25Params& p) {
     //  may be in flight on a stream that sa_batch_free does not wait for in order)
     if (rc == SA_OK) {
         Bm25Params pa = p;
-        pa.qlist = bt->d_iota; pa.nq = bt->n_grouped_rows; pa.tile0 = 0; pa.tile_end = warm;
+        pa.qlist = bt->d_iota; pa.nq = bt->n_grouped_rows; pa.tile0 = t0; pa.tile_end = t0 + warm;
         rc = sa_launch_bm25(ix, pa, st);
     }
-    if (rc == SA_OK && ix->n_tiles > warm) rc = sa_launch_bm25_groups(ix, bt, p, warm, st);
+    if (rc == SA_OK && ix->n_tiles > t0 + warm) rc = sa_launch_bm25_groups(ix, bt, p, t0 + warm, st);
     if (side) SA_HIP(hipStreamWaitEvent(st, bt->ev_side[1], 0));
     return rc;
 }
@@ -864,6 +913,9 @@ static int sa_batch_run_bm25(sa_batch* bt, u64* shard_out, bool deferred, bool u
     bt->last_route_stage = pl.route == SA_ROUTE_STAGED;
     bt->last_route_sparse = pl.route == SA_ROUTE_PRUNED;
     Bm25Params p = sa_batch_params(bt, pl);
+    if (bt->filter && sa_opt(bt->opts.trace, 0))
+        fprintf(stderr, "sa_batch: filtered run (%llu of %llu docs eligible): %s\n", (unsigned long long)bt->filter->count, (unsigned long long)bt->ix->n_docs,
+                pl.route == SA_ROUTE_STAGED ? "staged tiles" : pl.route == SA_ROUTE_GROUPED ? "grouped overlay + per-query tile kernel" : pl.pruned ? "per-query tile kernel" : "per-query tile kernel, unpruned");
     sa_batch_clear_state(bt, pl.pruned, pl.route == SA_ROUTE_PRUNED);
     const u32 slot = bt->ev_n % SA_EVENT_RING;
     SA_HIP(hipEventRecord(bt->ev0[slot], bt->st));

@@ -3,6 +3,7 @@
 #pragma once
 #include "sa_index.hpp"
 #include "sa_topk.hpp"
+#include "sa_filter.hpp"
 #include <vector>
 #include <time.h>
 
@@ -51,6 +52,9 @@ struct sa_batch {
     bool weights_ok = false;        // the current query set's weights are finite and >= 0, k1 >= 0, 0 <= b <= 1 (sa_batch_fill)
     u64 host_ns[4] = {0, 0, 0, 0};  // sa_batch_host_times
     std::vector<float> step_idf;    // sa_batch_step: the query set's weights, gathered from the index's idf table
+    // the document filter the batch ranks inside (sa_batch_set_filter), or null.  Setting one prepares the loaded query set again (from
+    // the upload image it was filled into): starting bounds, groups and the staged plan depend on the filter
+    std::shared_ptr<sa_filter_data> filter;
     // Everything a NEW set of queries changes on the device is one contiguous UPLOAD BLOCK (d_up) with a
     // page-locked host image: sa_batch_reset fills the image and enqueues ONE hipMemcpyAsync (+ the slice-table
     // kernel) -- no allocation, no blocking copy, no synchronisation.  The pointers below (d_terms ... d_bloom_off

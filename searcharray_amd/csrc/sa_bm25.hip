@@ -466,6 +466,12 @@ __device__ __forceinline__ void sa_bm25_tile_item(const Bm25Params& p, const u32
     }
     // the query terms with postings in this tile: phases of the others are skipped altogether
     u32 todo = (u32)__ballot(r_hi > r_lo);
+    if (p.filt) {                                               // (uniform) a tile without an eligible doc: as if no term had postings in it
+        constexpr u32 NB = (u32)TILE / 1024u;                   // (the filter's summary blocks: 1024 docs, SA_FILTER_BLOCK)
+        u32 any = 0;
+        for (u32 i = 0; i < NB; i++) { const u32 bi = tile * NB + i; any |= bi < p.filt_nblk ? p.filt_blk[bi] : 0u; }
+        if (!any) todo = 0u;
+    }
     auto lane64 = [](u64 x, u32 l) -> u64 {                      // value of lane l (wave-uniform l) in scalar registers
         const u32 a = (u32)__builtin_amdgcn_readlane((int)(u32)x, (int)l), b = (u32)__builtin_amdgcn_readlane((int)(u32)(x >> 32), (int)l);
         return ((u64)b << 32) | a;
@@ -757,6 +763,17 @@ __device__ __forceinline__ void sa_bm25_tile_item(const Bm25Params& p, const u32
 
     const u64 remain = p.n_docs - tile_base;
     const u32 tile_n = remain < (u64)TILE ? (u32)remain : (u32)TILE;
+    // the batch's document filter: the scores of the non-eligible docs are cleared BEFORE any selection, so that no excluded doc
+    // ever raises a slot, a histogram bin or the cached bound, or becomes a candidate
+    if (p.filt) {                                               // (uniform)
+#pragma unroll
+        for (int j = 0; j < E; j++) {
+            const u32 e = j * THREADS + tid;
+            const u64 w = e < tile_n ? p.filt[(tile_base + e) >> 6] : 0ull;
+            if (!((w >> (e & 63u)) & 1ull)) acc[e] = 0.f;
+        }
+        __syncthreads();
+    }
 
     // 3. dense drop-in output (SearchArray.score): coalesced tile store
     if (MODE == 0 && p.dense_out) {
@@ -1025,7 +1042,12 @@ extern "C" int sa_debug_probe_read(unsigned long long* out16, int clear) {
 
 // IDFN: cells of the item's weight table = queries x lanes-per-query of the table build (64: up to 4 overlaid terms per
 // query -- the BASELINE shape --, 128: anything else the host admits, n * tt <= 128)
-template <int TILE, int IDFN>
+// FILT: the batch has a document filter (sa_filter.hpp).  A tile without an eligible doc is left at once; the BASE cells of the
+// non-eligible docs are cleared (so base_max -- what every untouched doc scores at most -- speaks of eligible docs only); and since
+// the overlay adds to excluded docs as well (loose groups have no base at all), a doc's filter bit is part of the test that makes
+// it a survivor: no excluded doc reaches a candidate list or a histogram.  Pairs left to the per-query kernel find the filter
+// there.  The unfiltered instantiations contain none of it.
+template <int TILE, int IDFN, bool FILT>
 __global__ void __launch_bounds__(64, 4) sa_k_bm25_group_tiles(const Bm25Params p, const GroupParams gp) {
     constexpr int NH = SA_GRP_NH;
     static_assert(NH < (int)SA_GRPH_OVER && NH >= 8, "half count field");
@@ -1051,6 +1073,12 @@ __global__ void __launch_bounds__(64, 4) sa_k_bm25_group_tiles(const Bm25Params 
     const u32 trel = gp.tpx ? (r & 7u) * gp.tpx + chunk : chunk * 8u + (r & 7u);
     if (trel >= gp.n_tiles_run) return;
     const u32 tile = gp.tile0 + trel;
+    if constexpr (FILT) {
+        constexpr u32 NB = (u32)TILE / 1024u;                   // (the filter's summary blocks: 1024 docs)
+        u32 any = 0;
+        for (u32 i = 0; i < NB; i++) { const u32 bi = tile * NB + i; any |= bi < p.filt_nblk ? p.filt_blk[bi] : 0u; }
+        if (!any) return;                                       // (uniform) nothing eligible in this tile
+    }
     // a LOOSE group (bit 31 of the size): queries that share nothing -- no base, ALL their terms are overlaid on
     // cleared accumulators (0 + s0 = s0, so the sums are the same); what they share is the item's fixed cost
     const u32 row0 = gp.grp[3 * g], n_raw = gp.grp[3 * g + 1], n = n_raw & 0x7FFFFFFFu;
@@ -1242,6 +1270,27 @@ __global__ void __launch_bounds__(64, 4) sa_k_bm25_group_tiles(const Bm25Params 
         base_max = sa_wave_max_u32(lmax);
     }
 
+    if constexpr (FILT) {
+        if (!loose) {                                           // the base without the non-eligible docs (lane: four docs of one filter word per step)
+            float4* a4 = (float4*)accu;
+            u32 lmax = 0;
+#pragma unroll
+            for (int j = 0; j < TILE / 256; j++) {
+                const u32 doc0 = (u32)(j * 64 + (int)lane) * 4u;
+                const u64 fw = tile_base + doc0 < p.n_docs ? p.filt[(tile_base + doc0) >> 6] : 0ull;
+                const u32 bits = (u32)(fw >> (doc0 & 63u)) & 15u;
+                float4 v = a4[j * 64 + (int)lane];
+                v.x = (bits & 1u) ? v.x : 0.f; v.y = (bits & 2u) ? v.y : 0.f; v.z = (bits & 4u) ? v.z : 0.f; v.w = (bits & 8u) ? v.w : 0.f;
+                a4[j * 64 + (int)lane] = v;
+                const u32 m0 = __float_as_uint(v.x) > __float_as_uint(v.y) ? __float_as_uint(v.x) : __float_as_uint(v.y);
+                const u32 m1 = __float_as_uint(v.z) > __float_as_uint(v.w) ? __float_as_uint(v.z) : __float_as_uint(v.w);
+                const u32 m = m0 > m1 ? m0 : m1;
+                lmax = m > lmax ? m : lmax;
+            }
+            __builtin_amdgcn_wave_barrier();
+            base_max = sa_wave_max_u32(lmax);
+        }
+    }
     SA_PT(1);                                                   // first query requested, base built
     // queries left to the per-query kernel (work list at the end)
     u64 deferred = 0ull;
@@ -1353,7 +1402,14 @@ __global__ void __launch_bounds__(64, 4) sa_k_bm25_group_tiles(const Bm25Params 
             kb[i] = 0ull;
             if ((u32)i < nh) {
                 const u32 lim = ((u32)__builtin_amdgcn_readlane((int)X.dhi, i) >> (SA_GRPH_LIM_SHIFT - 32)) & 0x3Fu;
-                kb[i] = ballot(lane <= lim && rs[i] < (u32)TILE * 4u && !(ro[i] >> 31) && fin[i] >= thr);
+                bool el = true;
+                if constexpr (FILT) {                           // the doc's filter bit (this path is rare once the bound stands)
+                    const u32 dd = rs[i] >> 2;
+                    const bool inr = rs[i] < (u32)TILE * 4u && tile_base + dd < p.n_docs;
+                    const u64 fw = p.filt[inr ? (tile_base + dd) >> 6 : 0ull];
+                    el = inr && ((fw >> (dd & 63u)) & 1ull) != 0ull;
+                }
+                kb[i] = ballot(lane <= lim && rs[i] < (u32)TILE * 4u && !(ro[i] >> 31) && fin[i] >= thr && el);
             }
             c += (u32)__popcll(kb[i]);
         }
@@ -1778,18 +1834,24 @@ int sa_launch_bm25_groups(sa_index* ix, const sa_batch* bt, const Bm25Params& p,
 #else
     const u32 lds_pad = 0u;
 #endif
-#define SA_LAUNCH_GROUP(TILE, THREADS)                                                                                     \
+#define SA_LAUNCH_GROUP(TILE, THREADS, FILT)                                                                               \
     {                                                                                                                      \
-        if (blocks && small) hipLaunchKernelGGL((sa_k_bm25_group_tiles<TILE, 64>), dim3((u32)blocks), dim3(64), lds_pad, st, p, gp);       \
-        else if (blocks) hipLaunchKernelGGL((sa_k_bm25_group_tiles<TILE, 128>), dim3((u32)blocks), dim3(64), lds_pad, st, p, gp);            \
+        if (blocks && small && p.filt) hipLaunchKernelGGL((sa_k_bm25_group_tiles<TILE, 64, (FILT)>), dim3((u32)blocks), dim3(64), lds_pad, st, p, gp);   \
+        else if (blocks && p.filt) hipLaunchKernelGGL((sa_k_bm25_group_tiles<TILE, 128, (FILT)>), dim3((u32)blocks), dim3(64), lds_pad, st, p, gp);      \
+        else if (blocks && small) hipLaunchKernelGGL((sa_k_bm25_group_tiles<TILE, 64, false>), dim3((u32)blocks), dim3(64), lds_pad, st, p, gp);       \
+        else if (blocks) hipLaunchKernelGGL((sa_k_bm25_group_tiles<TILE, 128, false>), dim3((u32)blocks), dim3(64), lds_pad, st, p, gp);               \
         hipLaunchKernelGGL((sa_k_bm25_tiles_wl<TILE, THREADS>), dim3(wgrid), dim3(THREADS), 0, st, p, (const u64*)gp.wl,   \
                            (const u32*)gp.wl_cnt);                                                                         \
     }                                                                                                                      \
     break
     switch (ix->tile_docs) {
-        case 1024: SA_LAUNCH_GROUP(1024, 128);
-        case 2048: SA_LAUNCH_GROUP(2048, 64);
-        case 4096: SA_LAUNCH_GROUP(4096, 128);
+        case 1024: SA_LAUNCH_GROUP(1024, 128, true);
+        case 2048: SA_LAUNCH_GROUP(2048, 64, true);
+        // (4096-doc tiles: no filtered instantiation -- the kernel already misses its occupancy target there; the route rule keeps
+        //  filtered batches of such an index on the per-query kernel, sa_batch_plan)
+        case 4096:
+            if (p.filt) { sa_set_error("grouped kernel: no filtered instantiation for 4096-doc tiles"); return SA_ERR_STATE; }
+            SA_LAUNCH_GROUP(4096, 128, false);
         default:
             sa_set_error("unsupported tile_docs %u for the grouped kernel", ix->tile_docs);
             return SA_ERR_STATE;

@@ -69,6 +69,10 @@ struct Bm25Params {
     const u32* qlist;      // queries to scan (after the sparse path took the others), or null: all B
     u32 nq;                // number of queries to scan (= B without a list)
     const u32* nq_dev;     // the same on the device (sa_k_bm25_tiles_list)
+    // document filter of the batch (sa_filter.hpp), or null: every doc of the shard is eligible
+    const u64* filt;       // one bit per local doc
+    const u32* filt_blk;   // [filt_nblk] eligible docs per 1024-doc block
+    u32 filt_nblk;
     // outputs
     float* dense_out;      // [B][n_docs] or null
     u64* cand;             // [B][n_tiles][k] composite keys (global doc ids) or null

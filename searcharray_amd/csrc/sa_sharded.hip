@@ -312,6 +312,65 @@ extern "C" int sa_sharded_batch_fetch(sa_sharded_batch_t* bt, float* scores_out,
     return SA_OK;
 }
 
+// ---- document filters over all shards (Part 2b): one filter per shard, each shard's thread builds its own from the caller's
+//      global ids (sa_filter_create_from_rows ignores the ids of other shards) or its range of the global mask
+struct sa_sharded_filter {
+    sa_sharded* sh = nullptr;
+    std::vector<sa_filter_t*> parts;
+};
+
+extern "C" int sa_sharded_filter_destroy(sa_sharded_filter_t* f) {
+    if (!f) return SA_OK;
+    for (sa_filter_t* p : f->parts) sa_filter_destroy(p);       // (the shards' batches keep what they hold)
+    delete f;
+    return SA_OK;
+}
+
+static int sa_sharded_filter_build(sa_sharded* sh, const std::function<int(int, sa_filter_t**)>& make, sa_sharded_filter_t** out) {
+    sa_sharded_filter* f = new (std::nothrow) sa_sharded_filter();
+    if (!f) { sa_set_error("out of host memory"); return SA_ERR_NOMEM; }
+    f->sh = sh;
+    f->parts.assign((size_t)sh->G, nullptr);
+    const int rc = sh->all([&](int g) { return make(g, &f->parts[(size_t)g]); });
+    if (rc != SA_OK) {
+        const std::string keep = sa_last_error();
+        sa_sharded_filter_destroy(f);
+        sa_set_error("%s", keep.c_str());
+        return rc;
+    }
+    *out = f;
+    return SA_OK;
+}
+
+extern "C" int sa_sharded_filter_create_from_rows(sa_sharded_t* sh, const uint64_t* doc_ids, uint64_t n, sa_sharded_filter_t** out) {
+    SA_ARG(sh && out && (doc_ids || n == 0), "null argument");
+    return sa_sharded_filter_build(sh, [&](int g, sa_filter_t** part) { return sa_filter_create_from_rows(sh->shards[(size_t)g], doc_ids, n, part); }, out);
+}
+
+extern "C" int sa_sharded_filter_create_from_mask(sa_sharded_t* sh, const uint8_t* mask, uint64_t n_docs, sa_sharded_filter_t** out) {
+    SA_ARG(sh && out && (mask || n_docs == 0), "null argument");
+    SA_ARG(n_docs == sh->n_docs, "a filter mask has one byte per document of the corpus");
+    return sa_sharded_filter_build(sh, [&](int g, sa_filter_t** part) {
+        const u64 lo = sh->bounds[(size_t)g], hi = sh->bounds[(size_t)g + 1];
+        return sa_filter_create_from_mask(sh->shards[(size_t)g], mask ? mask + lo : nullptr, hi - lo, part);
+    }, out);
+}
+
+extern "C" int sa_sharded_filter_count(sa_sharded_filter_t* f, uint64_t* n_out) {
+    SA_ARG(f && n_out, "null argument");
+    uint64_t total = 0;
+    for (sa_filter_t* p : f->parts) { uint64_t c = 0; SA_TRY(sa_filter_count(p, &c)); total += c; }
+    *n_out = total;
+    return SA_OK;
+}
+
+// (collective like reset: a shard whose unfetched run was flagged redoes it before the filter changes, all shards together)
+extern "C" int sa_sharded_batch_set_filter(sa_sharded_batch_t* bt, sa_sharded_filter_t* f) {
+    SA_ARG(bt && bt->sh, "null batch");
+    SA_ARG(!f || (f->sh == bt->sh && f->parts.size() == bt->parts.size()), "the filter belongs to another sharded index");
+    return bt->sh->all([&](int g) { return sa_batch_set_filter(bt->parts[(size_t)g], f ? f->parts[(size_t)g] : nullptr); });
+}
+
 extern "C" int sa_sharded_batch_destroy(sa_sharded_batch_t* bt) {
     if (!bt) return SA_OK;
     if (bt->sh) {

@@ -94,6 +94,7 @@ struct StageParams {
     u64* cand; u32 cand_cap; u32* cand_cnt;
     u32* flag;                            // set when a probed term turns out essential (cannot happen: the run is then redone on another route)
     u32 tpx, tpw;                         // tiles per XCD, per workgroup
+    const u32* filt;                      // FILT instantiations: the batch's document filter (sa_filter.hpp) as 32-bit words, bit doc & 31 of word doc >> 5
 };
 
 sa_stagedir::~sa_stagedir() {
@@ -358,6 +359,7 @@ static int sa_stage_plan_slice(sa_batch* bt, char* base, u32* h_seed, const u32*
             const float sd1 = (im->h_topf[(size_t)t * SA_TOPF_NR + rank_idx] * w) * seed_scale;   // (the arithmetic of sa_k_make_bounds)
             if (sd1 > seed) seed = sd1;
         }
+        if (bt->filter) seed = 0.f;                              // (a filtered set: no starting bound, so every term is staged and none probed)
         seeds[q] = seed;
         u32 os[8];
         for (u32 s = 0; s < T; s++) os[s] = s;
@@ -604,7 +606,11 @@ typedef unsigned int sa_v4u __attribute__((vector_size(16)));
 struct alignas(8) StChunk { u32 dc, off; };    // a copy chunk: first stage cell | postings (1 .. 8) << 13; byte offset of its first posting from the stream base
 
 // KT: staged terms per thread (1: up to SA_ST_NT staged terms, the usual case; 2: up to SA_ST_UMAX)
-template <int TMAX, int KT>
+// FILT: the batch has a document filter.  A tile's filter words (at most SA_ST_BW) are read one tile ahead by every wave, staged in LDS
+// next to the presence bitmaps, and a candidate's bit is part of stage A's test: an excluded doc never becomes a survivor, so it never
+// reaches a histogram or a candidate list.  A tile without an eligible doc is passed over before its chunk list, its stage loads and
+// its query phase (its cursors and read-ahead move on as usual).  The unfiltered instantiations contain none of it.
+template <int TMAX, int KT, bool FILT>
 __global__ void __launch_bounds__(SA_ST_NT, 4) sa_k_bm25_stage(const StageParams sp) {
     constexpr int CAP = SaStCap<TMAX>::v;
     constexpr int NT = SA_ST_NT, NW = NT / SA_WAVE;
@@ -629,6 +635,7 @@ __global__ void __launch_bounds__(SA_ST_NT, 4) sa_k_bm25_stage(const StageParams
     __shared__ unsigned short s_cum[SA_ST_BMAX * TMAX];         // per query: candidates of the essential positions <= i
     __shared__ u32 s_qoff[SA_ST_BMAX + 1];                      // per query: its first candidate
     __shared__ alignas(16) u32 s_bits[NPBMAX * SA_ST_BW];   // presence bitmaps of the probed terms, this tile's docs
+    __shared__ u32 s_fbits[FILT ? SA_ST_BW : 1];            // FILT: the filter's words of this tile's docs
     __shared__ u32 s_ref[SA_ST_REF];
     __shared__ u32 s_nref, s_nb, s_nc;
     __shared__ u32 s_red[4 * NW];
@@ -811,11 +818,24 @@ __global__ void __launch_bounds__(SA_ST_NT, 4) sa_k_bm25_stage(const StageParams
         return q | (i << 8) | ((r - base) << 11);
     };
     __syncthreads();
+    // FILT: lane l < docs / 32 of every wave holds word l of the tile's filter words, read a tile ahead (the bitmap is allocated a whole
+    // block past the shard's last one: a tile's words are readable wherever it starts)
+    const u32 fwn = sp.docs >> 5;
+    u32 fw_next = 0u;
+    if constexpr (FILT) fw_next = lane < fwn ? sp.filt[(u32)(((u64)t_begin * sp.docs) >> 5) + lane] : 0u;
 
     for (u32 tile = t_begin; tile < t_end; tile += t_step) {
         const u64 tile_d0 = (u64)tile * sp.docs;
         const u64 tile_d1 = tile_d0 + sp.docs < sp.n_docs ? tile_d0 + sp.docs : sp.n_docs;
         SA_SPT(11);
+        bool tile_empty = false;
+        if constexpr (FILT) {
+            const u32 fw = fw_next;
+            const u32 tn = tile + t_step < t_end ? tile + t_step : tile;
+            fw_next = lane < fwn ? sp.filt[(u32)(((u64)tn * sp.docs) >> 5) + lane] : 0u;
+            tile_empty = __builtin_amdgcn_ballot_w64(fw != 0u) == 0ull;      // (the same in every wave: block-uniform)
+            if (wave == 0 && lane < (u32)SA_ST_BW) s_fbits[lane] = fw;      // (read by stage A, behind the barriers of this tile's pass)
+        }
         // postings of this thread's terms in this tile and the bound of their factors there, from what was read a tile ago
         u32 n_t[KT], tm[KT];
         {
@@ -852,6 +872,23 @@ __global__ void __launch_bounds__(SA_ST_NT, 4) sa_k_bm25_stage(const StageParams
             u32 n[KT];
 #pragma unroll
             for (int kx = 0; kx < KT; kx++) n[kx] = n_t[kx] - used[kx];
+            if constexpr (FILT) {
+                if (tile_empty) {                               // (uniform) nothing eligible here: only the reads for the next tile, and the cursors move on
+#pragma unroll
+                    for (int kx = 0; kx < KT; kx++) {
+                        const u32 kb = rowed[kx] ? 0xFFFFFFE0u : (src0[kx] + lo[kx] + n[kx]) << 3;
+                        const sa_v2u e = __builtin_amdgcn_raw_buffer_load_b64(r_dir, rowed[kx] ? cmi[kx] << 3 : 0xFFFFFFF0u, 0, 0);
+                        const u32 k0 = key_at(kb);
+                        nx[kx] = rowed[kx] ? e[1] : k0;
+                        ab[kx] = e[0];
+                        w1[kx] = key_at(kb + 8u);
+                        lo[kx] += n[kx];
+                    }
+                    pnx = __builtin_amdgcn_raw_buffer_load_b32(r_dir, NS + tid < U ? (pcmi << 3) + 4u : 0xFFFFFFF0u, 0, 0);
+                    g_raw = __hip_atomic_load(&sp.gthr[hasq ? tid : 0u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    break;
+                }
+            }
             u32 excl, exch, P, NC;
             {
                 u32 mine = 0, mch = 0;
@@ -1049,7 +1086,8 @@ __global__ void __launch_bounds__(SA_ST_NT, 4) sa_k_bm25_stage(const StageParams
                     }
 #pragma unroll
                     for (int c = 0; c < TMAX; c++) rem -= ((bwp[c] >> (od & 31u)) & 1u) ? 0.f : __fmul_rn(__uint_as_float(tmp[c]), wp[c]);
-                    const bool alive = valid && !(__fmul_rn(__fadd_rn(__fmul_rn(__uint_as_float((u32)vsrc), w_src), rem), SA_ST_MARGIN) < __uint_as_float(s_thr[q]));
+                    bool alive = valid && !(__fmul_rn(__fadd_rn(__fmul_rn(__uint_as_float((u32)vsrc), w_src), rem), SA_ST_MARGIN) < __uint_as_float(s_thr[q]));
+                    if constexpr (FILT) alive = alive && ((s_fbits[(od >> 5) & (u32)(SA_ST_BW - 1)] >> (od & 31u)) & 1u) != 0u;
                     SA_SPT(13);
                     const u64 m = (u64)__builtin_amdgcn_ballot_w64(alive);
                     if (m) {                                        // (wave-uniform)
@@ -1242,7 +1280,7 @@ int sa_launch_stage(sa_batch* bt, const Bm25Params& p, hipStream_t st) {
         sp.tpx = (sp.n_st + 7u) / 8u;
         const u32 wpx = grid / 8u;
         sp.tpw = (sp.tpx + wpx - 1u) / wpx;
-        // co-walking groups (option stage_cw, default 4; 1: private ranges): only when every staged term has a directory row -- a walked
+        // co-walking groups (option stage_cw, default 32; 1: private ranges): only when every staged term has a directory row -- a walked
         // term's cursor moves posting by posting and cannot skip the tiles of the group's other workgroups
         // (measured, BASELINE batch at 10 M docs, k = 10, groups of 1 / 2 / 4 / 8 / 16 / 32 / 64: 0.288 / 0.275 / 0.273 / 0.267 / 0.266 / 0.2575 /
         //  0.259 ms; L2 hit rate 6 % -> 75 %, traffic past the L2 1.53 -> 0.39 GB per launch: profiles/stage_kernel_cowalk_ab_r06.jsonl)
@@ -1251,12 +1289,15 @@ int sa_launch_stage(sa_batch* bt, const Bm25Params& p, hipStream_t st) {
         sp.cw = (x.all_rowed && cw > 1u && sp.tpw >= 2u) ? cw : 1u;
         if (sa_opt(bt->opts.trace, 0)) fprintf(stderr, "sa_launch_stage: rows %u..%u: %u workgroups, %u tiles of %u docs, %u per workgroup, co-walking groups of %u\n", x.q0, x.q0 + x.nq, grid, sp.n_st, sp.docs, sp.tpw, sp.cw);
         const bool one = x.NS <= (u32)SA_ST_NT;
+        sp.filt = (const u32*)p.filt;
+        if (sp.filt && (x.docs > 32u * (u32)SA_ST_BW || x.docs % 64u != 0u)) { sa_set_error("staged route: a filtered tile must be a multiple of 64 docs, at most 1024"); return SA_ERR_STATE; }
+        const bool filt = sp.filt != nullptr;
         if (x.tmax == 4) {
-            if (one) hipLaunchKernelGGL((sa_k_bm25_stage<4, 1>), dim3(grid), dim3(SA_ST_NT), 0, st, sp);
-            else hipLaunchKernelGGL((sa_k_bm25_stage<4, 2>), dim3(grid), dim3(SA_ST_NT), 0, st, sp);
+            if (one) { if (filt) hipLaunchKernelGGL((sa_k_bm25_stage<4, 1, true>), dim3(grid), dim3(SA_ST_NT), 0, st, sp); else hipLaunchKernelGGL((sa_k_bm25_stage<4, 1, false>), dim3(grid), dim3(SA_ST_NT), 0, st, sp); }
+            else { if (filt) hipLaunchKernelGGL((sa_k_bm25_stage<4, 2, true>), dim3(grid), dim3(SA_ST_NT), 0, st, sp); else hipLaunchKernelGGL((sa_k_bm25_stage<4, 2, false>), dim3(grid), dim3(SA_ST_NT), 0, st, sp); }
         } else {
-            if (one) hipLaunchKernelGGL((sa_k_bm25_stage<8, 1>), dim3(grid), dim3(SA_ST_NT), 0, st, sp);
-            else hipLaunchKernelGGL((sa_k_bm25_stage<8, 2>), dim3(grid), dim3(SA_ST_NT), 0, st, sp);
+            if (one) { if (filt) hipLaunchKernelGGL((sa_k_bm25_stage<8, 1, true>), dim3(grid), dim3(SA_ST_NT), 0, st, sp); else hipLaunchKernelGGL((sa_k_bm25_stage<8, 1, false>), dim3(grid), dim3(SA_ST_NT), 0, st, sp); }
+            else { if (filt) hipLaunchKernelGGL((sa_k_bm25_stage<8, 2, true>), dim3(grid), dim3(SA_ST_NT), 0, st, sp); else hipLaunchKernelGGL((sa_k_bm25_stage<8, 2, false>), dim3(grid), dim3(SA_ST_NT), 0, st, sp); }
         }
     }
     return SA_OK;

@@ -389,8 +389,43 @@ class DeviceIndex(_options.OptionsMixin):
         return ms.value, ab.value
 
     def batch(self, queries: np.ndarray, k: int = 10, k1: float = 1.2, b: float = 0.75,
-              idf: Optional[np.ndarray] = None, opts=None) -> "QueryBatch":
-        return QueryBatch(self, queries, k=k, k1=k1, b=b, idf=idf, opts=opts)
+              idf: Optional[np.ndarray] = None, opts=None, filter: Optional["DocFilter"] = None) -> "QueryBatch":
+        """a resident top-k batch; ``filter``: a ``DocFilter`` of this index the batch ranks inside (``QueryBatch.set_filter``)"""
+        bt = QueryBatch(self, queries, k=k, k1=k1, b=b, idf=idf, opts=opts)
+        if filter is not None:
+            bt.set_filter(filter)
+        return bt
+
+    def doc_filter(self, rows=None, mask=None) -> "DocFilter":
+        """A document filter of this index (``sa_filter_create_from_rows`` / ``_from_mask``) for ``batch(filter=...)``: ``rows`` are GLOBAL
+        doc ids in any order (duplicates allowed; ids outside this shard are ignored), ``mask`` is one truth value per local doc.
+        A filtered batch returns the top-k of the unfiltered scores with the non-eligible docs' scores set to 0 -- idf, average doc
+        length and corpus size stay those of the whole index, as a Solr ``fq`` leaves scoring alone.  This is NOT the reference's slice
+        semantics (``arr[rows].score`` recomputes docfreq inside the slice)."""
+        if (rows is None) == (mask is None):
+            raise ValueError("doc_filter takes either rows= or mask=")
+        h = ctypes.c_void_p()
+        if mask is not None:
+            m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+            if m.shape != (self.n_docs,):
+                raise ValueError(f"a filter mask has one entry per document ({self.n_docs}), got shape {m.shape}")
+            self._call("sa_filter_create_from_mask", self._h, m.ctypes.data_as(ctypes.c_void_p), self.n_docs, ctypes.byref(h))
+        else:
+            r = np.asarray(rows)
+            if r.size and r.dtype.kind not in "iu":
+                raise TypeError("filter rows must be integer doc ids")
+            if r.size and r.dtype.kind == "i" and int(r.min()) < 0:
+                raise ValueError("filter rows must be non-negative doc ids")
+            r = as_u64(r.reshape(-1))
+            self._call("sa_filter_create_from_rows", self._h, p_u64(r), r.size, ctypes.byref(h))
+        return DocFilter(self, h)
+
+    def term_filter(self, term_id: int) -> "DocFilter":
+        """the docs that contain term ``term_id`` (an unknown term: the empty filter): the ``fq=field:term`` building block"""
+        h = ctypes.c_void_p()
+        t = int(term_id)
+        self._call("sa_filter_create_from_term", self._h, t if 0 <= t < self.n_terms else NO_TERM, ctypes.byref(h))
+        return DocFilter(self, h)
 
     def queue(self, n_queries: int, n_terms: int, k: int = 10, k1: float = 1.2, b: float = 0.75, depth: int = 6, opts=None) -> "QueryQueue":
         """a query-set queue (``sa_queue_*``): ``depth`` batches of ``n_queries`` x ``n_terms`` behind one handle, stepped by a worker
@@ -433,6 +468,64 @@ class DeviceIndex(_options.OptionsMixin):
 
     def comm_barrier(self):
         self._call("sa_index_comm_barrier", self._h)
+
+
+class DocFilter:
+    """An immutable set of an index's documents on the device (``sa_filter_*``): ``DeviceIndex.doc_filter`` / ``term_filter`` build one,
+    ``&``, ``|``, ``-`` and ``~`` combine filters of the same index, ``batch(filter=...)`` / ``QueryBatch.set_filter`` rank inside one.
+    A batch keeps the filter it holds alive: ``close()`` while a batch uses it is safe."""
+
+    def __init__(self, index: "DeviceIndex", handle):
+        self.index = index
+        self.api = index.api
+        self._h = handle
+
+    def _need(self):
+        if self._h is None or not self._h.value:
+            raise ValueError("the DocFilter is closed")
+        return self._h
+
+    def count(self) -> int:
+        n = _lib.c_uint64(0)
+        self.api.call("sa_filter_count", self._need(), ctypes.byref(n))
+        return int(n.value)
+
+    def to_mask(self) -> np.ndarray:
+        out = np.zeros(self.index.n_docs, dtype=np.uint8)
+        self.api.call("sa_filter_fetch", self._need(), out.ctypes.data_as(ctypes.c_void_p))
+        return out.astype(bool)
+
+    def _combine(self, other: "DocFilter", op: int) -> "DocFilter":
+        if not isinstance(other, DocFilter):
+            return NotImplemented
+        h = ctypes.c_void_p()
+        self.api.call("sa_filter_combine", self._need(), other._need(), op, ctypes.byref(h))
+        return DocFilter(self.index, h)
+
+    def __and__(self, other):
+        return self._combine(other, 0)
+
+    def __or__(self, other):
+        return self._combine(other, 1)
+
+    def __sub__(self, other):
+        return self._combine(other, 2)
+
+    def __invert__(self):
+        h = ctypes.c_void_p()
+        self.api.call("sa_filter_not", self._need(), ctypes.byref(h))
+        return DocFilter(self.index, h)
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self.api.sa_filter_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class QueryBatch(_options.OptionsMixin):
@@ -485,6 +578,13 @@ class QueryBatch(_options.OptionsMixin):
         if q.shape != (self.B, self.T):
             raise ValueError(f"step takes [{self.B}][{self.T}] term ids")
         self._call("sa_batch_step", self._h, p_u32(q))
+
+    def set_filter(self, filter: Optional["DocFilter"]):
+        """rank inside ``filter`` (a ``DocFilter`` of this batch's index) from the next run on; ``None``: the whole index again.  Legal
+        whenever ``reset`` is; persists across ``reset`` / ``step`` (``sa_batch_set_filter``)"""
+        if filter is not None and not isinstance(filter, DocFilter):
+            raise TypeError("set_filter takes a DocFilter or None")
+        self._call("sa_batch_set_filter", self._h, filter._need() if filter is not None else None)
 
     def run(self, sync: bool = True):
         self._call("sa_batch_run", self._h, 1 if sync else 0)

@@ -717,7 +717,7 @@ class SearchArray(ExtensionArray):
         return "\n".join("        " + ln for ln in lines) + "\n"
 
     # -- batched top-k (no counterpart in the reference: its callers loop over score() + argpartition)
-    def search(self, queries, k: int = 10, similarity=default_bm25, devices=None) -> Tuple[np.ndarray, np.ndarray]:
+    def search(self, queries, k: int = 10, similarity=default_bm25, devices=None, filter=None) -> Tuple[np.ndarray, np.ndarray]:
         """Top-``k`` docs for many queries at once, without materialising dense score vectors:
         ``queries`` is a list of token lists (each scored as a disjunction: the sum of its terms' BM25,
         ``np.sum([arr.score(t) for t in q], axis=0)`` in reference terms) or a list of strings (each run
@@ -726,21 +726,64 @@ class SearchArray(ExtensionArray):
         Needs a stock BM25 similarity (``bm25_similarity(k1, b)``) and the whole array (not a slice).
         ``devices=[0, 1, ...]``: the index is cut into doc-id ranges, one per listed GPU, every shard is
         scored concurrently with the global statistics and the per-shard top-k are merged over RCCL
-        (searcharray_amd/sharded.py) -- same results as on one device."""
-        return self._topk(queries, k, similarity, phrases=False, devices=devices)
+        (searcharray_amd/sharded.py) -- same results as on one device.
+        ``filter``: rank inside a subset of the rows, as a Solr ``fq`` does -- a boolean mask of ``len(arr)``, an integer array of
+        row ids, or a reusable filter from :meth:`doc_filter` / :meth:`term_filter`.  The result is the top-``k`` of the unfiltered
+        scores with the excluded rows' scores set to 0: idf, average doc length and corpus size stay those of the WHOLE array.
+        This is not the reference's slice semantics -- ``arr[rows].score(...)`` recomputes docfreq inside the slice --, and
+        ``arr[rows].search(...)`` keeps raising."""
+        return self._topk(queries, k, similarity, phrases=False, devices=devices, filter=filter)
+
+    def _filter_arg(self, f):
+        """a mask / row-id filter argument, checked: (mask, None) or (None, rows)"""
+        n = len(self._core.doc_lens)
+        a = np.asarray(f)
+        if a.dtype == bool:
+            if a.shape != (n,):
+                raise ValueError(f"a boolean filter needs one entry per row ({n}), got shape {a.shape}")
+            return a, None
+        if a.size == 0:
+            return None, np.zeros(0, dtype=np.uint64)
+        if a.dtype.kind not in "iu" or a.ndim != 1:
+            raise ValueError("filter: a boolean mask of len(arr), a 1-d integer array of row ids, or a DocFilter")
+        if int(a.min()) < 0 or int(a.max()) >= n:
+            raise ValueError(f"filter row ids must lie in [0, {n})")
+        return None, a.astype(np.uint64)
+
+    def doc_filter(self, mask_or_rows):
+        """A reusable document filter for ``search(filter=...)`` from a boolean mask of ``len(arr)`` or an array of row ids (a
+        ``DocFilter`` on the device: ``&``, ``|``, ``-``, ``~``, ``count()``, ``to_mask()``).  E.g. a pandas boolean column:
+        ``arr.doc_filter((df.category == "x").to_numpy())``."""
+        if self._rows is not None:
+            raise ValueError("filters are built on the whole indexed array, not on a slice")
+        mask, rows = self._filter_arg(mask_or_rows)
+        dev = self._core.device()
+        return dev.doc_filter(mask=mask) if mask is not None else dev.doc_filter(rows=rows)
+
+    def term_filter(self, token: str):
+        """the rows that contain ``token`` as a reusable filter (``fq=field:token``); an unknown token gives the empty filter, as
+        ``score`` gives zeros"""
+        if self._rows is not None:
+            raise ValueError("filters are built on the whole indexed array, not on a slice")
+        return self._core.device().term_filter(self._term_id(self._check_token_arg(token)))
 
     def search_phrases(self, phrases, k: int = 10, similarity=default_bm25, devices=None, slop=0) -> Tuple[np.ndarray, np.ndarray]:
         """Like :meth:`search`, each query a phrase: the top-``k`` of ``arr.score(phrase, slop=slop)`` (``slop``: one
         value or one per phrase).  Any phrase ``score`` takes is fine -- repeated tokens, long phrases, slop."""
         return self._topk(phrases, k, similarity, phrases=True, devices=devices, slop=slop)
 
-    def _topk(self, queries, k, similarity, phrases, devices=None, slop=0):
+    def _topk(self, queries, k, similarity, phrases, devices=None, slop=0, filter=None):
         if getattr(similarity, "kind", None) != "bm25":
             raise ValueError("batched search needs a stock BM25 similarity (bm25_similarity(k1, b))")
         if self._rows is not None:
             raise ValueError("batched search runs on the whole indexed array, not on a slice")
         toks = [list(self.tokenizer(q)) if isinstance(q, str) else [self._check_token_arg(t) for t in q] for q in queries]
         B = len(toks)
+        from .device_index import DocFilter
+        from .sharded import ShardedDocFilter
+        fmask = frows = None
+        if filter is not None and not isinstance(filter, (DocFilter, ShardedDocFilter)):
+            fmask, frows = self._filter_arg(filter)                 # (checked before anything is launched)
         if B == 0 or len(self._core.doc_lens) == 0:
             return np.zeros((B, k), np.float32), np.full((B, k), NO_DOC, np.uint64)
         # (an explicit device list is honoured even when it names ONE device: a one-shard handle on that GPU)
@@ -755,11 +798,27 @@ class SearchArray(ExtensionArray):
             for i, q in enumerate(ids):
                 mat[i, :len(q)] = q
             batch = dev.batch(mat, k=k, k1=similarity.k1, b=similarity.b)
+        own = None
         try:
+            if filter is not None:
+                sharded = devices is not None and len(devices) >= 1
+                if isinstance(filter, ShardedDocFilter) or (isinstance(filter, DocFilter) and not sharded):
+                    if filter.index is not dev:
+                        raise ValueError("the filter was built for another index (or another device list)")
+                    f = filter
+                elif isinstance(filter, DocFilter):                 # a single-device filter of this array, searched sharded
+                    if filter.index is not self._core._device:
+                        raise ValueError("the filter was built for another index")
+                    f = own = dev.doc_filter(mask=filter.to_mask())
+                else:
+                    f = own = dev.doc_filter(mask=fmask) if fmask is not None else dev.doc_filter(rows=frows)
+                batch.set_filter(f)
             batch.run()
             return batch.fetch()
         finally:
             batch.close()
+            if own is not None:
+                own.close()
 
     def positions(self, token: str, key=None) -> List[np.ndarray]:
         """positions of ``token`` per doc (reference postings.py:682-687)."""

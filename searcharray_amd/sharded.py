@@ -143,7 +143,31 @@ class ShardedIndex:
         return np.concatenate(self.map(lambda g, s: s.bm25_phrase_dense(terms, k1=k1, b=b, slop=slop, idf=idf)))
 
     # -- resident top-k batches
-    def batch(self, queries: np.ndarray, k: int = 10, k1: float = 1.2, b: float = 0.75, opts=None) -> "ShardedBatch":
+    def doc_filter(self, rows=None, mask=None) -> "ShardedDocFilter":
+        """A document filter over all shards (``sa_sharded_filter_create_from_rows`` / ``_from_mask``): GLOBAL doc ids in any order, or one
+        truth value per document of the whole corpus; the library fans it out to one filter per shard.  Semantics as
+        ``DeviceIndex.doc_filter``: scoring keeps the statistics of the whole corpus."""
+        if (rows is None) == (mask is None):
+            raise ValueError("doc_filter takes either rows= or mask=")
+        ct = _lib.ctypes
+        h = ct.c_void_p()
+        if mask is not None:
+            m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+            if m.shape != (self.n_docs,):
+                raise ValueError(f"a filter mask has one entry per document ({self.n_docs}), got shape {m.shape}")
+            self.api.call("sa_sharded_filter_create_from_mask", self._h, m.ctypes.data_as(ct.c_void_p), self.n_docs, ct.byref(h))
+        else:
+            r = np.asarray(rows)
+            if r.size and r.dtype.kind not in "iu":
+                raise TypeError("filter rows must be integer doc ids")
+            if r.size and (int(r.min()) < 0 or int(r.max()) >= self.n_docs):
+                raise ValueError("filter rows out of range")
+            r = _lib.as_u64(r.reshape(-1))
+            self.api.call("sa_sharded_filter_create_from_rows", self._h, _lib.p_u64(r), r.size, ct.byref(h))
+        return ShardedDocFilter(self, h)
+
+    def batch(self, queries: np.ndarray, k: int = 10, k1: float = 1.2, b: float = 0.75, opts=None,
+              filter: Optional["ShardedDocFilter"] = None) -> "ShardedBatch":
         q = np.asarray(queries, dtype=np.int64)
         if q.ndim != 2:
             raise ValueError("queries must be [B][T] term ids")
@@ -153,7 +177,10 @@ class ShardedIndex:
         with _options.creating(self.api, _options.Options(self._opts, opts)):
             self.api.call("sa_sharded_batch_create", self._h, _lib.p_u32(terms), _lib.p_f32(idf), q.shape[0], q.shape[1], int(k),
                           np.float32(k1), np.float32(b), _lib.ctypes.byref(h))
-        return ShardedBatch(self, h, q.shape[0], int(k), n_terms=q.shape[1], opts=_options.Options(self._opts, opts))
+        bt = ShardedBatch(self, h, q.shape[0], int(k), n_terms=q.shape[1], opts=_options.Options(self._opts, opts))
+        if filter is not None:
+            bt.set_filter(filter)
+        return bt
 
     def phrase_batch(self, phrases, k: int = 10, k1: float = 1.2, b: float = 0.75, slop=0, opts=None) -> "ShardedBatch":
         ct = _lib.ctypes
@@ -196,6 +223,34 @@ class ShardedIndex:
             pass
 
 
+class ShardedDocFilter:
+    """one document filter per shard behind one handle (``sa_sharded_filter_*``); the shards' batches keep what they hold alive"""
+
+    def __init__(self, index: ShardedIndex, handle):
+        self.index, self.api, self._h = index, index.api, handle
+
+    def _need(self):
+        if self._h is None or not self._h.value:
+            raise ValueError("the filter is closed")
+        return self._h
+
+    def count(self) -> int:
+        n = _lib.c_uint64(0)
+        self.api.call("sa_sharded_filter_count", self._need(), _lib.ctypes.byref(n))
+        return int(n.value)
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self.api.sa_sharded_filter_destroy(self._h)
+            self._h = _lib.ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class ShardedBatch(_options.OptionsMixin):
     """One resident query batch per shard behind one handle (``sa_sharded_batch_*``); ``run`` = score every shard +
     all-gather + merge, ``fetch`` = the merged top-k.  Follows the thread's scoped options and ``set_options`` like a
@@ -214,6 +269,12 @@ class ShardedBatch(_options.OptionsMixin):
         idf = _lib.as_f32(self.index.idfs(q.reshape(-1)).reshape(q.shape))
         terms = _lib.as_u32(np.where((q >= 0) & (q < self.index.n_terms), q, NO_TERM).astype(np.uint32))
         self._call("sa_sharded_batch_reset", self._h, _lib.p_u32(terms), _lib.p_f32(idf))
+
+    def set_filter(self, filter: Optional[ShardedDocFilter]):
+        """rank inside ``filter`` (``ShardedIndex.doc_filter``) from the next run on; ``None``: the whole corpus again"""
+        if filter is not None and not isinstance(filter, ShardedDocFilter):
+            raise TypeError("set_filter takes a filter of ShardedIndex.doc_filter or None")
+        self._call("sa_sharded_batch_set_filter", self._h, filter._need() if filter is not None else None)
 
     def run(self, sync: bool = True):
         self._call("sa_sharded_batch_run", self._h, 1 if sync else 0)

@@ -596,6 +596,25 @@ int sa_vec_destroy(sa_vec_t* v);
 int sa_vec_zero(sa_vec_t* v);
 int sa_vec_copy(sa_vec_t* dst, const sa_vec_t* src);                          /* same kind and length */
 int sa_vec_fetch(sa_vec_t* v, void* host_out);                               /* n * 8 or n * 4 bytes */
+/* host -> vector: n * 8 or n * 4 bytes (the counterpart of sa_vec_fetch) */
+int sa_vec_store(sa_vec_t* v, const void* host_in);
+/* The k best entries of a vector, selected on the device (sa_vec_topk.hip): how a multi-field query ends without copying its
+ * n scores to the host.
+ * Eligible: entries with value > 0 (NaN and values <= 0 never rank) whose bit is set in `filter` (NULL: all).
+ * Order: value descending, then index ascending.  scores_out: k values of the vector's own type (float64 or float32; a 32-bit
+ * vector is read as float32), docs_out: k indices; slots past the eligible entries hold 0 and 2^64-1, as sa_batch_fetch pads.
+ * found_out (may be NULL): the number of eligible entries, whatever k is (Solr's numFound).
+ * 1 <= k <= 1024 (SA_KMAX); k may exceed n; n < 2^32.  The filter must live on the vector's device and cover exactly v->n documents (it
+ * may have been built for ANY index of that length: the rows of a frame's fields align); otherwise SA_ERR_ARG.
+ * Exact and deterministic: float64 values are ranked on all 64 bits, and the result is a function of (vector, filter, k) alone.
+ * The selection streams the vector a few times (radix select on the pair (value bits, index), 12 bits a pass; blocks of 1024
+ * documents the filter leaves empty are not read); its scratch belongs to the vector (allocated by the first call, freed by
+ * sa_vec_destroy), so repeated calls allocate nothing.  Synchronous like the rest of Part 4; safe to call from several threads
+ * at once on different vectors. */
+int sa_vec_topk(sa_vec_t* v, sa_filter_t* filter, int k, void* scores_out, uint64_t* docs_out, uint64_t* found_out);
+/* diagnostics: the passes over the vector the last sa_vec_topk of `v` made (0: no call yet, or the last call read nothing: an
+ * empty vector or an empty filter) */
+int sa_vec_topk_passes(const sa_vec_t* v, int* passes_out);
 /* the next dense call on `ix` from this thread writes (result * boost if has_boost) into out32 on the
  * device instead of to its host `out`; out32 == NULL clears a pending selection */
 int sa_index_select_vec(sa_index_t* ix, sa_vec_t* out32, float boost, int has_boost);

@@ -164,6 +164,9 @@ PROTOTYPES = {
     "sa_vec_zero": (c_int, [c_void_p]),
     "sa_vec_copy": (c_int, [c_void_p, c_void_p]),
     "sa_vec_fetch": (c_int, [c_void_p, c_void_p]),
+    "sa_vec_store": (c_int, [c_void_p, c_void_p]),
+    "sa_vec_topk": (c_int, [c_void_p, c_void_p, c_int, c_void_p, u64p, u64p]),
+    "sa_vec_topk_passes": (c_int, [c_void_p, POINTER(c_int)]),
     "sa_index_select_vec": (c_int, [c_void_p, c_void_p, c_float, c_int]),
     "sa_vec_dismax_acc": (c_int, [c_void_p, c_void_p, c_void_p]),
     "sa_vec_clause": (c_int, [c_void_p, c_void_p, c_double, c_void_p, c_void_p]),

@@ -9,18 +9,11 @@
 // np.zeros(n) accumulators (term-centric), float32 throughout where it stacks float32 arrays
 // (field-centric); every operation rounds once (no FMA contraction) -- so the result equals the host
 // path bit for bit.  The API is synchronous: every call returns with its work done.
-#include "sa_index.hpp"
+#include "sa_vec.hpp"
 #include "../../include/searcharray_hip.h"
 #include <new>
 
-struct sa_vec {
-    int device = 0;
-    u64 n = 0;
-    int f64 = 0;
-    void* d = nullptr;
-};
-
-static hipStream_t sa_vec_stream(int device) {
+hipStream_t sa_vec_stream(int device) {
     static std::mutex mu;
     static hipStream_t streams[64] = {};
     std::lock_guard<std::mutex> g(mu);
@@ -51,6 +44,7 @@ extern "C" int sa_vec_create(int device, uint64_t n, int is_f64, sa_vec_t** out)
 extern "C" int sa_vec_destroy(sa_vec_t* v) {
     if (!v) return SA_OK;
     hipSetDevice(v->device);
+    sa_vec_topk_release(v);
     if (v->d) hipFree(v->d);
     delete v;
     return SA_OK;

@@ -793,6 +793,37 @@ class DeviceVec:
         self.api.call("sa_vec_fetch", self._h, out.ctypes.data_as(ctypes.c_void_p))
         return out
 
+    def store(self, array) -> "DeviceVec":
+        """host -> vector (``sa_vec_store``): ``len(self)`` values, converted to the vector's dtype"""
+        a = np.ascontiguousarray(array, dtype=np.float64 if self.f64 else np.float32)
+        if a.shape != (self.n,):
+            raise ValueError(f"store needs {self.n} values, got shape {a.shape}")
+        self.api.call("sa_vec_store", self._h, a.ctypes.data_as(ctypes.c_void_p))
+        return self
+
+    def topk(self, k: int, filter: Optional["DocFilter"] = None) -> Tuple[np.ndarray, np.ndarray, int]:
+        """The ``k`` best entries, selected on the device (``sa_vec_topk``): ``(scores, rows, found)``.  Only values > 0 rank (NaN
+        never does), inside ``filter`` if one is given (a ``DocFilter`` over ``len(self)`` documents on this vector's device);
+        order: value descending, then row ascending.  ``scores`` has the vector's dtype, ``rows`` is uint64; slots past the eligible
+        entries hold 0 and ``NO_DOC``.  ``found`` counts the eligible entries whatever ``k`` is.  1 <= k <= 1024."""
+        k = int(k)
+        if not 1 <= k <= 1024:
+            raise ValueError("k must be in 1 .. 1024")
+        if filter is not None and not isinstance(filter, DocFilter):
+            raise TypeError("filter must be a DocFilter")
+        scores = np.zeros(k, dtype=np.float64 if self.f64 else np.float32)
+        rows = np.full(k, NO_DOC, dtype=np.uint64)
+        found = _lib.c_uint64(0)
+        self.api.call("sa_vec_topk", self._h, filter._need() if filter is not None else None, k,
+                      scores.ctypes.data_as(ctypes.c_void_p), p_u64(rows), ctypes.byref(found))
+        return scores, rows, int(found.value)
+
+    def topk_passes(self) -> int:
+        """passes over the vector the last ``topk`` made (diagnostics)"""
+        n = ctypes.c_int(0)
+        self.api.call("sa_vec_topk_passes", self._h, ctypes.byref(n))
+        return int(n.value)
+
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
             self.api.sa_vec_destroy(self._h)

@@ -16,17 +16,22 @@ With stock BM25 similarities on whole (unsliced) arrays the combination itself r
 straight into a device vector and only the final result crosses PCIe.  The arithmetic follows numpy's
 operation for operation, so both routes return identical arrays (tests/test_solr.py runs each scenario
 through both).  Anything else -- custom similarity callables, slices -- takes the host route.
+
+``edismax_search`` (no counterpart in the reference, whose callers rank the dense result with ``np.argpartition``) returns the
+top ``k`` rows of the same scores, optionally inside a document filter (Solr's ``fq``): on the device route the combined vector
+is selected in HBM (``sa_vec_topk``, csrc/sa_vec_topk.hip) and never crosses PCIe.
 """
 from __future__ import annotations
 
 import ctypes
 import re
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Sequence, Tuple, Union
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import pandas as pd
 
+from .device_index import NO_DOC, DocFilter
 from .postings import SearchArray
 from .similarity import Similarity, default_bm25
 
@@ -308,6 +313,74 @@ class _DeviceCombiner:
             call("sa_vec_add_where", scores._h, extra._h, scores._h)
 
 
+class _Plan(NamedTuple):
+    """an edismax call with its arguments resolved: what both routes and both entry points start from"""
+    fields: List[_Field]
+    per_field: Dict[str, List[str]]
+    similarity: Dict[str, Similarity]
+    n_terms: int
+    term_centric: bool
+    mm: str
+    phases: tuple
+
+
+def _plan(frame, q, qf, mm, pf, pf2, pf3, q_op, similarity) -> _Plan:
+    def as_list(x):
+        return x if isinstance(x, list) else [x]
+
+    query_boosts = parse_field_boosts(as_list(qf))
+    phrase_boosts = parse_field_boosts(as_list(pf)) if pf else {}
+    bigram_boosts = parse_field_boosts(pf2) if pf2 else {}
+    trigram_boosts = parse_field_boosts(pf3) if pf3 else {}
+    mm = "1" if mm is None else (f"{mm}" if isinstance(mm, int) else mm)
+    if q_op == "AND":
+        mm = "100%"
+    if not isinstance(similarity, dict):
+        similarity = {field: similarity for field in query_boosts}
+    for field in query_boosts:
+        similarity.setdefault(field, default_bm25)
+
+    n_terms, per_field, term_centric = parse_query_terms(frame, q, list(query_boosts))
+    fields = [_Field(name, boost, get_field(frame, name), per_field[name], similarity[name])
+              for name, boost in query_boosts.items()]
+    phases = ((phrase_boosts, None), (bigram_boosts, 2), (trigram_boosts, 3))
+    return _Plan(fields, per_field, similarity, n_terms, term_centric, mm, phases)
+
+
+def _device_scores(comb: _DeviceCombiner, plan: _Plan, tie: float):
+    """the combined scores as a device vector of ``comb`` (closed with it) and the explain string, which is the host route's"""
+    if plan.term_centric:
+        need = parse_min_should_match(plan.n_terms, spec=plan.mm)
+        scores_v = comb.term_centric(plan.n_terms, need, tie)
+    else:
+        scores_v = comb.field_centric(plan.mm, tie)
+    explain = _explain_main(plan.fields, plan.n_terms, plan.mm, plan.term_centric)
+    mask0 = comb.vec(scores_v.f64)
+    mask0.copy_from(scores_v)
+    for boosts, n in plan.phases:
+        comb.phrase_phase(scores_v, mask0, plan.per_field, boosts, n)
+        explain += _explain_phase(plan.per_field, boosts, n)
+    return scores_v, explain
+
+
+def _host_scores(frame: pd.DataFrame, plan: _Plan, tie: float) -> Tuple[np.ndarray, str]:
+    fields = plan.fields
+    if plan.term_centric:
+        scores, explain = _term_centric(fields, len(frame), plan.n_terms, plan.mm, tie)
+    else:
+        scores, explain = _field_centric(fields, len(frame), plan.mm, tie)
+
+    # phrase boosts only look at (and only add to) the docs the main query matched
+    hit = scores > 0
+    matched = {f.name: f.array[hit] for f in fields}
+    for boosts, n in plan.phases:
+        extra, text = _phrase_phase(matched, plan.per_field, boosts, plan.similarity, n)
+        explain += text
+        if extra is not None:
+            scores[np.where(scores)[0]] += extra
+    return scores, explain
+
+
 def edismax(frame: pd.DataFrame,
             q: str,
             qf: List[str],
@@ -330,61 +403,127 @@ def edismax(frame: pd.DataFrame,
     one per field.  ps / ps2 / ps3 are accepted for signature parity and, as in the reference, unused.
     use_device: None picks the GPU combination whenever it applies (stock BM25, unsliced arrays); False
     forces the host route.  Returns ``(scores[len(frame)], explain string)`` -- float64 term-centric,
-    float32 field-centric, as the reference."""
-    def as_list(x):
-        return x if isinstance(x, list) else [x]
-
-    query_boosts = parse_field_boosts(as_list(qf))
-    phrase_boosts = parse_field_boosts(as_list(pf)) if pf else {}
-    bigram_boosts = parse_field_boosts(pf2) if pf2 else {}
-    trigram_boosts = parse_field_boosts(pf3) if pf3 else {}
-    mm = "1" if mm is None else (f"{mm}" if isinstance(mm, int) else mm)
-    if q_op == "AND":
-        mm = "100%"
-    if not isinstance(similarity, dict):
-        similarity = {field: similarity for field in query_boosts}
-    for field in query_boosts:
-        similarity.setdefault(field, default_bm25)
-
-    n_terms, per_field, term_centric = parse_query_terms(frame, q, list(query_boosts))
-    fields = [_Field(name, boost, get_field(frame, name), per_field[name], similarity[name])
-              for name, boost in query_boosts.items()]
-    phases = ((phrase_boosts, None), (bigram_boosts, 2), (trigram_boosts, 3))
+    float32 field-centric, as the reference.  :func:`edismax_search` ranks the same scores on the device
+    and returns the top ``k`` instead of the dense vector."""
+    plan = _plan(frame, q, qf, mm, pf, pf2, pf3, q_op, similarity)
     if use_device is None:
-        use_device = _DeviceCombiner.usable(fields, len(frame))
+        use_device = _DeviceCombiner.usable(plan.fields, len(frame))
     if use_device:
-        # everything stays in HBM until the final vector; the explain string is the host route's
-        comb = _DeviceCombiner(fields, len(frame))
+        # everything stays in HBM until the final vector
+        comb = _DeviceCombiner(plan.fields, len(frame))
         try:
-            if term_centric:
-                need = parse_min_should_match(n_terms, spec=mm)
-                scores_v = comb.term_centric(n_terms, need, tie)
-            else:
-                scores_v = comb.field_centric(mm, tie)
-            explain = _explain_main(fields, n_terms, mm, term_centric)
-            mask0 = comb.vec(scores_v.f64)
-            mask0.copy_from(scores_v)
-            for boosts, n in phases:
-                comb.phrase_phase(scores_v, mask0, per_field, boosts, n)
-                explain += _explain_phase(per_field, boosts, n)
+            scores_v, explain = _device_scores(comb, plan, tie)
             return scores_v.fetch(), explain
         finally:
             comb.close()
+    return _host_scores(frame, plan, tie)
 
-    if term_centric:
-        scores, explain = _term_centric(fields, len(frame), n_terms, mm, tie)
+
+class SearchHits(NamedTuple):
+    """what :func:`edismax_search` returns: the ``k`` best rows of the frame, best first"""
+    scores: np.ndarray       # float64 (term-centric) or float32 (field-centric), as edismax's vector; 0 past the hits
+    rows: np.ndarray         # uint64 row positions in the frame; 2**64 - 1 (NO_DOC) past the hits
+    found: int               # rows with a score > 0 inside fq, whatever k is (Solr's numFound)
+    explain: str
+
+
+def _fq_mask(frame: pd.DataFrame, fq) -> Optional[np.ndarray]:
+    """``fq`` as a boolean mask of the frame's rows (None: no filter); checks it as ``SearchArray.search(filter=)`` does"""
+    if fq is None:
+        return None
+    if isinstance(fq, DocFilter):
+        if fq.index.n_docs != len(frame):
+            raise ValueError(f"fq covers {fq.index.n_docs} documents, the frame has {len(frame)} rows")
+        return fq.to_mask()
+    a = np.asarray(fq)
+    n = len(frame)
+    if a.dtype == bool:
+        if a.shape != (n,):
+            raise ValueError(f"a boolean fq needs one entry per row ({n}), got shape {a.shape}")
+        return a
+    if a.size == 0:
+        return np.zeros(n, dtype=bool)
+    if a.dtype.kind not in "iu" or a.ndim != 1:
+        raise ValueError("fq: a boolean mask of len(frame), a 1-d integer array of row ids, or a DocFilter")
+    if int(a.min()) < 0 or int(a.max()) >= n:
+        raise ValueError(f"fq row ids must lie in [0, {n})")
+    mask = np.zeros(n, dtype=bool)
+    mask[a] = True
+    return mask
+
+
+def _host_topk(scores: np.ndarray, mask: Optional[np.ndarray], k: int):
+    """numpy selection in the device's order: positives only, value descending, then row ascending"""
+    keep = scores > 0
+    if mask is not None:
+        keep &= mask
+    idx = np.flatnonzero(keep)
+    order = idx[np.lexsort((idx, -scores[idx]))[:k]]
+    out_s = np.zeros(k, dtype=scores.dtype)
+    out_r = np.full(k, NO_DOC, dtype=np.uint64)
+    out_s[:len(order)] = scores[order]
+    out_r[:len(order)] = order
+    return out_s, out_r, int(len(idx))
+
+
+def edismax_search(frame: pd.DataFrame,
+                   q: str,
+                   qf: List[str],
+                   k: int = 10,
+                   fq=None,
+                   mm: Optional[Union[str, int]] = None,
+                   pf: Optional[List[str]] = None,
+                   pf2: Optional[List[str]] = None,
+                   pf3: Optional[List[str]] = None,
+                   ps2: int = 0,
+                   ps3: int = 0,
+                   ps: int = 0,
+                   tie: float = 0.0,
+                   q_op: str = "OR",
+                   similarity: Union[Similarity, Dict[str, Similarity]] = default_bm25,
+                   use_device: Optional[bool] = None) -> SearchHits:
+    """:func:`edismax` ranked: the ``k`` best rows instead of one score per row.  On the device route (whenever ``edismax``
+    combines on the GPU) the score vector is built exactly as ``edismax`` builds it and then selected in HBM
+    (``DeviceVec.topk``): k scores and k row ids cross PCIe, not ``len(frame)`` floats.  Same keyword arguments as ``edismax``.
+
+    Returns ``SearchHits(scores, rows, found, explain)``: only scores > 0 rank, ordered by score descending, then row
+    ascending; ``scores`` has the dtype of ``edismax``'s vector; slots past the hits hold score 0 and row ``2**64 - 1``;
+    ``found`` counts the rows that could rank whatever ``k`` is.  1 <= k <= 1024.
+
+    ``fq``: rank inside a subset of the rows, as a Solr ``fq`` does -- a boolean mask of ``len(frame)``, an integer array of
+    row ids, or a reusable ``DocFilter`` built from any ``SearchArray`` column of the frame (``arr.doc_filter(...)``,
+    ``arr.term_filter("tok")`` and their ``& | - ~`` combinations).  The result is the top-``k`` of the unfiltered ``edismax``
+    scores with the excluded rows' scores set to 0: idf, average doc length and corpus size stay those of the WHOLE columns,
+    and ``mm`` and the phrase-boost phases (which use the docs the main query matched) do not see the filter.  This is not the
+    reference's slice semantics (``frame[rows]`` recomputes docfreq inside the slice).
+
+    Not covered: lists of queries per call, sharded frames (``devices=``), and filters for phrase batches and the queue."""
+    k = int(k)
+    if not 1 <= k <= 1024:
+        raise ValueError("k must be in 1 .. 1024")
+    plan = _plan(frame, q, qf, mm, pf, pf2, pf3, q_op, similarity)
+    if use_device is None:
+        use_device = _DeviceCombiner.usable(plan.fields, len(frame))
+    if not use_device:
+        mask = _fq_mask(frame, fq)
+        scores, explain = _host_scores(frame, plan, tie)
+        return SearchHits(*_host_topk(scores, mask, k), explain)
+    own = None                                                   # a filter made here from a mask or row ids
+    if fq is None or isinstance(fq, DocFilter):
+        filt = fq
+        if filt is not None and filt.index.n_docs != len(frame):
+            raise ValueError(f"fq covers {filt.index.n_docs} documents, the frame has {len(frame)} rows")
     else:
-        scores, explain = _field_centric(fields, len(frame), mm, tie)
-
-    # phrase boosts only look at (and only add to) the docs the main query matched
-    hit = scores > 0
-    matched = {f.name: f.array[hit] for f in fields}
-    for boosts, n in phases:
-        extra, text = _phrase_phase(matched, per_field, boosts, similarity, n)
-        explain += text
-        if extra is not None:
-            scores[np.where(scores)[0]] += extra
-    return scores, explain
+        mask = _fq_mask(frame, fq)         # (checked before anything is launched)
+        filt = own = plan.fields[0].array._core.device().doc_filter(mask=mask)
+    comb = _DeviceCombiner(plan.fields, len(frame))
+    try:
+        scores_v, explain = _device_scores(comb, plan, tie)
+        return SearchHits(*scores_v.topk(k, filter=filt), explain)
+    finally:
+        comb.close()
+        if own is not None:
+            own.close()
 
 
 def _explain_main(fields: List[_Field], n_terms: int, mm: str, term_centric: bool) -> str:

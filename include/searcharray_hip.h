@@ -413,6 +413,22 @@ int sa_filter_destroy(sa_filter_t* filter);
  * sa_batch_last_route says 0).  A filter of another index -> SA_ERR_ARG.  Phrase batches and the timing option no_topk do not take
  * a filter (SA_ERR_UNSUPPORTED). */
 int sa_batch_set_filter(sa_batch_t* batch, sa_filter_t* filter);
+/* MINIMUM-SHOULD-MATCH (Solr `mm`, `q.op=AND`) for BM25 batches.  min_match: n_queries values in CALLER query order (NULL clears them).
+ * With value m, query i keeps only the documents that match at least m of its query SLOTS; every other document scores 0, as under a
+ * filter.  A slot matches a document when its own contribution fl(factor x weight) is > 0; slots count separately (a term given twice
+ * counts twice); padding slots and unknown terms never match, so m = n_query_terms with an unknown term returns nothing, and so does m
+ * above the number of slots.  m <= 1 is the plain disjunction.  Scores are those of the whole index, bit for bit, in the same order;
+ * with a filter as well a document must pass both tests.
+ * The contract of sa_batch_set_filter: the values apply from the next run on, including runs of the query set already loaded (it is
+ * prepared again); an unfetched run that was flagged is redone first, with the state it ran with; the values persist across
+ * sa_batch_reset / sa_batch_step like the filter and the options -- row i of every later query set gets value i.
+ * Route: a batch with any value > 1 runs on the per-query tile kernels' counting instantiations only (sa_batch_last_route says 0 whatever
+ * the options stage / sparse / group say) and without starting bounds (sa_batch_seeds reports 0).  A tile in which fewer than m of a
+ * query's terms have postings is skipped before a posting is read; with sa_batch_stats enabled, sparse_candidates_out counts those
+ * skipped (tile, query) items instead.  A batch whose values are all <= 1 runs exactly as without the call.
+ * SA_ERR_UNSUPPORTED: phrase batches; the timing option no_topk; an index whose tile size has no counting kernels (they exist for 1024,
+ * 2048, 4096 and 8192 docs per tile).  The query-set queue (Part 2c) has no such call. */
+int sa_batch_set_min_match(sa_batch_t* batch, const uint32_t* min_match);
 
 /* ---- Part 2c: a query-set QUEUE (csrc/sa_queue.hip).  A ring of `depth` batches of the same shape behind one handle, fed by a WORKER
  * THREAD of the library: sa_queue_submit copies a set of B x T term ids (weights come from the index's idf table, sa_index_set_idf_table,
@@ -440,6 +456,9 @@ int sa_batch_profile(sa_batch_t* batch, double* kernel_ms_out, uint64_t* alg_byt
  * the sparse path scores (one extra atomic each: not for timed runs); returns the count accumulated
  * since the previous call and how many queries of the last run were answered without a tile scan. */
 int sa_batch_stats(sa_batch_t* batch, int enable, uint64_t* sparse_candidates_out, uint64_t* sparse_queries_out);
+/* DIAGNOSTICS ONLY (BM25 batches; nothing on the serving path needs it, tests use it to see that per-query tables are exercised with
+ * a row order that is not the identity): out[r] = the caller query that device row r of the current query set holds (n_queries values) */
+int sa_batch_row_order(sa_batch_t* batch, uint32_t* out);
 /* How the exhaustive path groups the batch (csrc/sa_bm25.hip, sa_k_bm25_group_tiles): out[0] = groups, out[1] = queries
  * in groups, out[2] = of them in groups that share their first term (the others are loose groups), out[3] = queries
  * left to the per-query kernel.  Diagnostics for benchmarks and tests; no reference counterpart. */
@@ -581,6 +600,9 @@ int sa_sharded_filter_count(sa_sharded_filter_t* filter, uint64_t* n_out);
 int sa_sharded_filter_destroy(sa_sharded_filter_t* filter);
 /* sa_batch_set_filter on every shard's batch (NULL clears) */
 int sa_sharded_batch_set_filter(sa_sharded_batch_t* batch, sa_sharded_filter_t* filter);
+/* sa_batch_set_min_match with the same n_queries values on every shard's batch (NULL clears): the count is per document and shards are
+ * doc ranges */
+int sa_sharded_batch_set_min_match(sa_sharded_batch_t* batch, const uint32_t* min_match);
 
 /* ------------------------------------------------------------------------------------- */
 /* Part 4 -- dense vectors on the device: the combine step of Solr-style multi-field queries */

@@ -42,8 +42,12 @@ static sa_plan sa_batch_plan(const sa_batch* bt, bool deferred, bool unpruned) {
     // overlay or the per-query tile kernels.  Dynamic pruning does not look at the filter, so the rule keeps a filtered batch off it
     // whatever the options say; and it starts without the rank-table bounds, which hold for the whole corpus only.
     const bool filtered = bt->filter != nullptr;
+    // A batch with minimum-should-match values > 1 (sa_batch_set_min_match) is stricter still: only the per-query tile kernels count the
+    // slots a doc matched, so its route is SA_ROUTE_TILES whatever the options say -- never staged, grouped or dynamically pruned -- and
+    // it starts without the rank-table bounds, which count docs that the test may exclude.
+    const bool mm = bt->mm_on;
     // (the grouped kernel and the starting bounds need non-negative scores: the sign bit is a mark)
-    pl.group = sa_opt(o.group, 1) != 0 && bt->weights_ok && sa_grouped_tiles(ix->tile_docs);
+    pl.group = !mm && sa_opt(o.group, 1) != 0 && bt->weights_ok && sa_grouped_tiles(ix->tile_docs);   // (no row groups for a set that cannot take the overlay)
     pl.seed_wanted = bt->weights_ok && bt->impacts && bt->k <= 1024u && sa_opt(o.term_seed, 1) != 0 && sa_opt(o.sparse, -1) != 1;
     // the staged-tile route (sa_stage.hip) is asked for: option `stage` = 1, or unset while `sparse` is unset too (a caller that
     // sets `sparse` chooses between the two older routes)
@@ -73,7 +77,7 @@ static sa_plan sa_batch_plan(const sa_batch* bt, bool deferred, bool unpruned) {
     // all of them frequent: 0.62 ms exhaustive vs 1.68 ms pruned at k = 10): the exhaustive path is the default whenever
     // at least half of the batch's queries are in groups of either sort.
     // (the overlay's filtered instantiations exist for 1024- and 2048-doc tiles)
-    const bool grouped = bt->n_groups && impact_route && sa_opt(o.group, 1) != 0 && !(filtered && ix->tile_docs > 2048u);
+    const bool grouped = !mm && bt->n_groups && impact_route && sa_opt(o.group, 1) != 0 && !(filtered && ix->tile_docs > 2048u);
     // Unset, `sparse` follows the measurements: pruning pays while the shard holds many docs per requested
     // result (10 M docs: 2.2x at k = 10, 1.9x at k = 100, but the exhaustive kernel is 1.2x faster at k = 1000;
     // 1.25 M docs, k = 1000: exhaustive 1.8x faster) -- on from 32768 docs per result (8192 since round 6, below).  sparse = 1 / 0 force it.
@@ -84,13 +88,13 @@ static sa_plan sa_batch_plan(const sa_batch* bt, bool deferred, bool unpruned) {
     const bool sparse_wanted = sparse_opt >= 0 ? sparse_opt != 0 : (ix->n_docs >= (u64)bt->k * 8192ull && !impact_route);
     // Round 6: the staged-tile route (sa_stage.hip) takes every query set it has a plan for -- distinct terms staged in LDS once
     // per tile, the queries answered from there; it needs the histogram bound and the impact stream like the grouped kernel
-    const bool stage = bt->stage_ok && pl.stage_wanted && hist_possible && pl.imp && !no_topk && ix->avg_doc_len != 0.f;
-    const bool sparse = !stage && !filtered && sparse_wanted && hist_possible && ix->tile_docs <= 8192 && ix->avg_doc_len != 0.f && ix->n_tiles > 0;
+    const bool stage = !mm && bt->stage_ok && pl.stage_wanted && hist_possible && pl.imp && !no_topk && ix->avg_doc_len != 0.f;
+    const bool sparse = !stage && !filtered && !mm && sparse_wanted && hist_possible && ix->tile_docs <= 8192 && ix->avg_doc_len != 0.f && ix->n_tiles > 0;
     // (a run that checks overflow on the host keeps the slot bound up to k = 32)
     pl.hist = hist_possible && (sparse || stage || deferred || bt->k > 32);
     pl.route = stage ? SA_ROUTE_STAGED : sparse ? SA_ROUTE_PRUNED : grouped && pl.hist ? SA_ROUTE_GROUPED : SA_ROUTE_TILES;
     // the bounds the queries start with (exhaustive kernels only: the pruning path derives its own from the lead terms)
-    pl.seed = pl.hist && !sparse && bt->seed_on && pl.imp && !filtered;
+    pl.seed = pl.hist && !sparse && bt->seed_on && pl.imp && !filtered && !mm;
     // (with the histogram bound a wave appends all its survivors, so the worst case is not bounded by k)
     pl.may_overflow = pl.pruned && (bt->cap_limited || pl.hist) && ix->n_tiles > 0;
     return pl;
@@ -269,6 +273,7 @@ static int sa_batch_alloc_bm25(sa_batch* bt) {
     bt->st_bytes = sa_stage_upload_bytes((u32)B, (u32)T);
     off = (off + 15) & ~(size_t)15;
     const size_t o_st = take(bt->st_bytes);
+    const size_t o_mm = take(B * 4);
     SA_TRY(sa_batch_alloc_upload(bt, off));
     char* u = bt->d_up;
     bt->d_p1_off = (u64*)(u + o_p1); bt->d_bloom_off = (u64*)(u + o_boff);
@@ -278,6 +283,7 @@ static int sa_batch_alloc_bm25(sa_batch* bt) {
     bt->d_bloom_shift = (u32*)(u + o_bsh);
     bt->d_seed = (u32*)(u + o_seed);
     bt->d_st = u + o_st;
+    bt->d_min_match = (u32*)(u + o_mm);              // (behind d_terms: Bm25Params::min_match_off)
     {
         std::vector<u32> iota(B);
         for (u32 i = 0; i < B; i++) iota[i] = i;
@@ -631,12 +637,16 @@ static int sa_batch_fill(sa_batch* bt, const uint32_t* terms, const float* idf) 
         memcpy(&h_idf[(size_t)r * T], &idf[(size_t)bt->perm[r] * T], T * sizeof(float));
         h_perm[r] = bt->perm[r];
     }
+    {                                                           // minimum-should-match: row r gets the value of caller query perm[r]
+        u32* h_mm = (u32*)at(bt->d_min_match);
+        for (u32 r = 0; r < B; r++) h_mm[r] = bt->min_match.empty() ? 0u : bt->min_match[bt->perm[r]];
+    }
     memset(h_grpd, 0, (size_t)3 * B * sizeof(u32));
     if (!h_grp.empty()) memcpy(h_grpd, h_grp.data(), h_grp.size() * sizeof(u32));     // (at most B groups)
     memset(at(bt->d_seed), 0, (size_t)B * sizeof(u32));
     if (pl.seed_wanted) sa_impacts_ensure_topf(ix, bt->impacts.get());
     const bool tables = pl.seed_wanted && bt->impacts->d_topf;   // the rank tables and the terms' largest factors exist
-    bt->seed_on = tables && !bt->filter;                        // (a filtered set starts from 0: the tables' bounds count docs the filter may exclude)
+    bt->seed_on = tables && !bt->filter && !bt->mm_on;          // (a filtered or minimum-should-match set starts from 0: the tables' bounds count docs the test may exclude)
     // the staged-tile route's plan (sa_stage.hip): distinct terms, per-query bound tables and the starting bounds, formed on the
     // host into the same upload.  A set that has one does not need the slice table: sa_k_make_bounds is left out of the step and
     // only runs if the run takes another route after all (sa_batch_ensure_bounds)
@@ -644,7 +654,7 @@ static int sa_batch_fill(sa_batch* bt, const uint32_t* terms, const float* idf) 
     bt->st_dir.reset();
     bt->st_slices.clear();
     // (a filtered set is planned with zero starting bounds: every term staged, none probed)
-    if (tables && pl.stage_wanted) SA_TRY(sa_stage_plan(bt, img, h_terms, h_idf));
+    if (tables && pl.stage_wanted && !bt->mm_on) SA_TRY(sa_stage_plan(bt, img, h_terms, h_idf));
     // the pruning tables: now, if the run will prune (the route rule, now that the groups and the staged plan are known); else on demand
     if (sa_batch_plan(bt, true, false).route == SA_ROUTE_PRUNED) sa_batch_fill_prune_tables(bt, img);
     else { bt->sparse_ok = false; bt->bloom_bytes = 0; bt->sparse_p1_total = 0; bt->sparse_p2_max = 0; }
@@ -705,6 +715,25 @@ extern "C" int sa_batch_reset(sa_batch_t* bt, const uint32_t* terms, const float
     return sa_batch_fill(bt, terms, idf);
 }
 
+// The loaded query set, prepared again for a changed batch state (filter, minimum-should-match): back in caller order from the upload
+// image it was filled into (device-row order + the row order; the image's copy to the device has left the host buffer when its event
+// has fired; the fill writes the OTHER image).
+static int sa_batch_refill(sa_batch* bt) {
+    const u32 last = (bt->up_n - 1u) & 1u;
+    SA_HIP(hipEventSynchronize(bt->ev_up[last]));
+    const char* img = bt->h_up[last];
+    const u32* r_terms = (const u32*)(img + ((const char*)bt->d_terms - bt->d_up));
+    const float* r_idf = (const float*)(img + ((const char*)bt->d_idf - bt->d_up));
+    const size_t T = bt->T;
+    std::vector<u32> terms((size_t)bt->B * T);
+    std::vector<float> idf((size_t)bt->B * T);
+    for (u32 r = 0; r < bt->B; r++) {
+        memcpy(&terms[(size_t)bt->perm[r] * T], &r_terms[(size_t)r * T], T * sizeof(u32));
+        memcpy(&idf[(size_t)bt->perm[r] * T], &r_idf[(size_t)r * T], T * sizeof(float));
+    }
+    return sa_batch_fill(bt, terms.data(), idf.data());
+}
+
 // Part 2b: the batch ranks inside `f` from its next run on (null: the whole index).  The loaded query set is prepared again -- its
 // starting bounds, groups and staged plan belong to the filter state they were made for.
 extern "C" int sa_batch_set_filter(sa_batch_t* bt, sa_filter_t* f) {
@@ -725,21 +754,41 @@ extern "C" int sa_batch_set_filter(sa_batch_t* bt, sa_filter_t* f) {
     if (bt->filter) SA_HIP(hipStreamSynchronize(bt->st));       // (runs in flight read the bitmap this call may release)
     bt->filter = f ? f->d : nullptr;
     if (sa_opt(bt->opts.trace, 0)) fprintf(stderr, "sa_batch_set_filter: %llu of %llu docs eligible\n", f ? (unsigned long long)f->d->count : (unsigned long long)ix->n_docs, (unsigned long long)ix->n_docs);
-    // the loaded set, back in caller order, from the upload image it was filled into (device-row order + the row order; the image's
-    // copy to the device has left the host buffer when its event has fired; the fill below writes the OTHER image)
-    const u32 last = (bt->up_n - 1u) & 1u;
-    SA_HIP(hipEventSynchronize(bt->ev_up[last]));
-    const char* img = bt->h_up[last];
-    const u32* r_terms = (const u32*)(img + ((const char*)bt->d_terms - bt->d_up));
-    const float* r_idf = (const float*)(img + ((const char*)bt->d_idf - bt->d_up));
-    const size_t T = bt->T;
-    std::vector<u32> terms((size_t)bt->B * T);
-    std::vector<float> idf((size_t)bt->B * T);
-    for (u32 r = 0; r < bt->B; r++) {
-        memcpy(&terms[(size_t)bt->perm[r] * T], &r_terms[(size_t)r * T], T * sizeof(u32));
-        memcpy(&idf[(size_t)bt->perm[r] * T], &r_idf[(size_t)r * T], T * sizeof(float));
+    return sa_batch_refill(bt);
+}
+
+// Minimum-should-match: from its next run on the batch keeps, for caller query i, only the docs that match at least min_match[i] of
+// the query's slots (null: every doc, as before).  The contract of sa_batch_set_filter: the loaded query set is prepared again --
+// route, starting bounds, groups and the staged plan belong to the state they were made for -- and the values persist across
+// sa_batch_reset / sa_batch_step (row i of every later set gets value i).
+extern "C" int sa_batch_set_min_match(sa_batch_t* bt, const uint32_t* min_match) {
+    SA_ARG(bt && bt->ix, "null batch");
+    if (bt->kind != 0) { sa_set_error("sa_batch_set_min_match: phrase batches do not take minimum-should-match"); return SA_ERR_UNSUPPORTED; }
+    sa_index* ix = bt->ix;
+    std::lock_guard<std::mutex> g(ix->mu);
+    SA_HIP(hipSetDevice(ix->device));
+    bool on = false;
+    for (u32 i = 0; min_match && i < bt->B; i++) on |= min_match[i] > 1u;
+    if (on && sa_opt(bt->opts.no_topk, 0) != 0) { sa_set_error("sa_batch_set_min_match: not with the timing option no_topk"); return SA_ERR_UNSUPPORTED; }
+    if (on && !sa_min_match_tiles(ix->tile_docs)) {
+        sa_set_error("sa_batch_set_min_match: no counting kernel for tile_docs %u (1024, 2048, 4096, 8192)", ix->tile_docs);
+        return SA_ERR_UNSUPPORTED;
     }
-    return sa_batch_fill(bt, terms.data(), idf.data());
+    if (!min_match && bt->min_match.empty()) return SA_OK;
+    // (as in sa_batch_reset: an unfetched run that was flagged is redone first -- with the values and the tables it ran with)
+    if (bt->res_pending && bt->unfetched) {
+        SA_HIP(hipEventSynchronize(bt->ev_res));
+        SA_TRY(sa_batch_redo_if_flagged(bt));
+    }
+    if (min_match) bt->min_match.assign(min_match, min_match + bt->B);
+    else bt->min_match.clear();
+    bt->mm_on = on;
+    if (sa_opt(bt->opts.trace, 0)) {
+        u32 n = 0;
+        for (u32 v : bt->min_match) n += v > 1u ? 1u : 0u;
+        fprintf(stderr, "sa_batch_set_min_match: %u of %u queries with a value > 1\n", n, bt->B);
+    }
+    return sa_batch_refill(bt);
 }
 
 extern "C" int sa_index_set_idf_table(sa_index_t* ix, const float* idf_per_term, uint32_t n_terms) {
@@ -833,6 +882,7 @@ static Bm25Params sa_batch_params(const sa_batch* bt, const sa_plan& pl) {
     p.seed = pl.seed ? bt->d_seed : nullptr;
     p.qlist = nullptr; p.nq = bt->B;
     if (bt->filter) { p.filt = bt->filter->d_words; p.filt_blk = bt->filter->d_blk; p.filt_nblk = bt->filter->n_blocks; }
+    if (bt->mm_on) { p.min_match_off = (u32)((const char*)bt->d_min_match - (const char*)bt->d_terms); p.stats = bt->d_stats; }     // (sa_batch_stats then counts the (tile, query) items skipped)
     return p;
 }
 
@@ -916,6 +966,11 @@ static int sa_batch_run_bm25(sa_batch* bt, u64* shard_out, bool deferred, bool u
     if (bt->filter && sa_opt(bt->opts.trace, 0))
         fprintf(stderr, "sa_batch: filtered run (%llu of %llu docs eligible): %s\n", (unsigned long long)bt->filter->count, (unsigned long long)bt->ix->n_docs,
                 pl.route == SA_ROUTE_STAGED ? "staged tiles" : pl.route == SA_ROUTE_GROUPED ? "grouped overlay + per-query tile kernel" : pl.pruned ? "per-query tile kernel" : "per-query tile kernel, unpruned");
+    if (bt->mm_on && sa_opt(bt->opts.trace, 0)) {
+        u32 n = 0;
+        for (u32 v : bt->min_match) n += v > 1u ? 1u : 0u;
+        fprintf(stderr, "sa_batch: minimum-should-match run: %u of %u queries with a value > 1: %s\n", n, bt->B, pl.pruned ? "per-query tile kernel" : "per-query tile kernel, unpruned");
+    }
     sa_batch_clear_state(bt, pl.pruned, pl.route == SA_ROUTE_PRUNED);
     const u32 slot = bt->ev_n % SA_EVENT_RING;
     SA_HIP(hipEventRecord(bt->ev0[slot], bt->st));
@@ -1258,6 +1313,16 @@ extern "C" int sa_batch_last_route(sa_batch_t* bt, int* pruned_out) {
     SA_ARG(bt && bt->ix && pruned_out, "null argument");
     std::lock_guard<std::mutex> g(bt->ix->mu);
     *pruned_out = bt->last_route_stage ? 2 : bt->last_route_sparse ? 1 : 0;
+    return SA_OK;
+}
+
+// Diagnostics: the caller query that each device row of the current set holds (row r -> out[r]); tests check that per-query tables
+// written through this order (sa_batch_set_min_match) are exercised with an order that is not the identity.
+extern "C" int sa_batch_row_order(sa_batch_t* bt, uint32_t* out) {
+    SA_ARG(bt && bt->ix && out, "null argument");
+    SA_ARG(bt->kind == 0, "sa_batch_row_order takes a BM25 batch");
+    std::lock_guard<std::mutex> g(bt->ix->mu);
+    for (u32 r = 0; r < bt->B; r++) out[r] = bt->perm[r];
     return SA_OK;
 }
 

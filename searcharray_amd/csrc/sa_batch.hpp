@@ -55,6 +55,12 @@ struct sa_batch {
     // the document filter the batch ranks inside (sa_batch_set_filter), or null.  Setting one prepares the loaded query set again (from
     // the upload image it was filled into): starting bounds, groups and the staged plan depend on the filter
     std::shared_ptr<sa_filter_data> filter;
+    // minimum-should-match (sa_batch_set_min_match): per CALLER query, the number of query slots a doc must match; empty: none set.
+    // Every fill writes the values in device-row order into the upload block (d_min_match).  mm_on: some value is > 1 -- the batch
+    // then runs on the per-query tile kernels' counting instantiations only, without starting bounds (sa_batch_plan)
+    std::vector<u32> min_match;
+    bool mm_on = false;
+    u32* d_min_match = nullptr;     // [B] in the upload block
     // Everything a NEW set of queries changes on the device is one contiguous UPLOAD BLOCK (d_up) with a
     // page-locked host image: sa_batch_reset fills the image and enqueues ONE hipMemcpyAsync (+ the slice-table
     // kernel) -- no allocation, no blocking copy, no synchronisation.  The pointers below (d_terms ... d_bloom_off

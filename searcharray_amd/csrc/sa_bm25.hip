@@ -401,8 +401,15 @@ __host__ __device__ constexpr int sa_tile_tab_floats() {
     return IMP ? (NW * SA_HBINS / 2 > 64 ? NW * SA_HBINS / 2 : 64) : SA_SAT_NTF * SA_SAT_WMAX;
 }
 
-template <int TILE, int THREADS, int MODE, bool IMP>
-__device__ __forceinline__ void sa_bm25_tile_item(const Bm25Params& p, const u32 tile, const u32 qi, u64* smem, float* s_tab) {
+// MM: minimum-should-match (p.min_match_off, sa_batch_set_min_match).  The item keeps a byte per doc beside the accumulators (`mc`, TILE +
+// one spare per lane -- shared by the waves, never read for a result --, handed in by the kernel like the accumulators): the number of query slots whose own product was > 0.  A tile in
+// which fewer than m of the query's terms have postings is left before a posting is read; the accumulators of docs that matched fewer
+// than m slots are cleared BEFORE the filter clear and any selection, so everything downstream is unchanged.  A term phase touches a
+// doc at most once and phases are separated by barriers: the update is a plain byte read-modify-write (ds_read_u8 / ds_write_b8 --
+// byte stores of different lanes into one dword do not disturb each other).  The instantiations without MM contain none of it.
+template <int TILE, int THREADS, int MODE, bool IMP, bool MM = false>
+__device__ __forceinline__ void sa_bm25_tile_item(const Bm25Params& p, const u32 tile, const u32 qi, u64* smem, float* s_tab,
+                                                  unsigned char* mc = nullptr) {
     constexpr int NW = THREADS / SA_WAVE;
     constexpr int E = TILE / THREADS;
     constexpr int CAP = (TILE >= 8192) ? 2048 : TILE / 4;      // candidate list capacity (MODE 0)
@@ -472,6 +479,15 @@ __device__ __forceinline__ void sa_bm25_tile_item(const Bm25Params& p, const u32
         for (u32 i = 0; i < NB; i++) { const u32 bi = tile * NB + i; any |= bi < p.filt_nblk ? p.filt_blk[bi] : 0u; }
         if (!any) todo = 0u;
     }
+    u32 mm = 0;                                                 // (uniform) slots a doc of this query must match
+    if constexpr (MM) {
+        mm = ((const u32*)((const char*)p.terms + p.min_match_off))[q];
+        // fewer than mm of the query's terms have postings in this tile: no doc of it can match mm slots
+        if (todo != 0u && (u32)__builtin_popcount(todo) < mm) {
+            todo = 0u;
+            if (p.stats && tid == 0) atomicAdd(&p.stats[q], 1u);
+        }
+    }
     auto lane64 = [](u64 x, u32 l) -> u64 {                      // value of lane l (wave-uniform l) in scalar registers
         const u32 a = (u32)__builtin_amdgcn_readlane((int)(u32)x, (int)l), b = (u32)__builtin_amdgcn_readlane((int)(u32)(x >> 32), (int)l);
         return ((u64)b << 32) | a;
@@ -500,7 +516,9 @@ __device__ __forceinline__ void sa_bm25_tile_item(const Bm25Params& p, const u32
                 const float norm = __fmul_rn(k1, __fadd_rn(one_minus_b, __fmul_rn(bb, __fdiv_rn(dl, avgdl))));
                 sat = __fdiv_rn(tf, __fadd_rn(tf, norm));
             }
-            acc[d] = __fadd_rn(acc[d], __fmul_rn(sat, idf));
+            const float prod = __fmul_rn(sat, idf);
+            acc[d] = __fadd_rn(acc[d], prod);
+            if constexpr (MM) mc[d] = (unsigned char)(mc[d] + (prod > 0.f ? 1u : 0u));
         }
     };
     // Impact stream: the factor is in the posting and a posting is valid iff its doc lies in this tile
@@ -545,10 +563,17 @@ __device__ __forceinline__ void sa_bm25_tile_item(const Bm25Params& p, const u32
         const u32 d0 = (u32)(v.x >> 32) - tile_base_b, d1 = (u32)(v.y >> 32) - tile_base_b;
         const u32 s0 = d0 < (u32)TILE * 4u ? d0 : spare, s1 = d1 < (u32)TILE * 4u ? d1 : spare;
         const float v0 = acc_at(s0), v1 = acc_at(s1);
-        const float w0 = __fadd_rn(v0, __fmul_rn(__uint_as_float((u32)v.x), idf));
-        const float w1 = __fadd_rn(v1, __fmul_rn(__uint_as_float((u32)v.y), idf));
+        const float p0 = __fmul_rn(__uint_as_float((u32)v.x), idf);
+        const float w0 = __fadd_rn(v0, p0);
+        const float p1 = __fmul_rn(__uint_as_float((u32)v.y), idf);
+        const float w1 = __fadd_rn(v1, p1);
         acc_at(s0) = w0;
         acc_at(s1) = w1;
+        if constexpr (MM) {                                     // (byte s >> 2 beside accumulator s; a sentinel's product is NaN: not > 0)
+            const u32 c0 = mc[s0 >> 2], c1 = mc[s1 >> 2];
+            mc[s0 >> 2] = (unsigned char)(c0 + (p0 > 0.f ? 1u : 0u));
+            mc[s1 >> 2] = (unsigned char)(c1 + (p1 > 0.f ? 1u : 0u));
+        }
     };
     auto score_batch = [&](const Batch& b, u64 lo, u64 hi, u32 first, float idf) {
         const u64 a0 = lo & ~1ull;
@@ -578,6 +603,20 @@ __device__ __forceinline__ void sa_bm25_tile_item(const Bm25Params& p, const u32
             }
 #pragma unroll
             for (int i = 0; i < 2 * PF; i++) acc_at(slot[i]) = val[i];
+            // the same batch of eight on the count bytes, all reads before all writes as above -- and behind the accumulators'
+            // stores, when the eight sums have left the registers (in front of them: 131 VGPRs, a wave per SIMD less)
+            if constexpr (MM) {
+                u32 cnt[2 * PF];
+#pragma unroll
+                for (int i = 0; i < 2 * PF; i++) cnt[i] = mc[slot[i] >> 2];
+#pragma unroll
+                for (int u = 0; u < PF; u++) {
+                    cnt[2 * u] += __fmul_rn(__uint_as_float((u32)b.v[u].x), idf) > 0.f ? 1u : 0u;
+                    cnt[2 * u + 1] += __fmul_rn(__uint_as_float((u32)b.v[u].y), idf) > 0.f ? 1u : 0u;
+                }
+#pragma unroll
+                for (int i = 0; i < 2 * PF; i++) mc[slot[i] >> 2] = (unsigned char)cnt[i];
+            }
             return;
         }
         const u32 r_lo = (u32)(lo - a0), r_hi = (u32)(hi - a0);     // the slice inside its hull
@@ -702,6 +741,10 @@ __device__ __forceinline__ void sa_bm25_tile_item(const Bm25Params& p, const u32
             if (!cleared) {                                     // first group: clear the accumulators behind the loads
 #pragma unroll
                 for (int j = 0; j < E; j++) acc[j * THREADS + tid] = 0.f;
+                if constexpr (MM) {                             // ... and the match counts, four docs per store
+#pragma unroll
+                    for (int j = 0; j < E / 4; j++) ((u32*)mc)[j * THREADS + tid] = 0u;
+                }
                 __syncthreads();
                 cleared = true;
             }
@@ -763,6 +806,18 @@ __device__ __forceinline__ void sa_bm25_tile_item(const Bm25Params& p, const u32
 
     const u64 remain = p.n_docs - tile_base;
     const u32 tile_n = remain < (u64)TILE ? (u32)remain : (u32)TILE;
+    // minimum-should-match: a doc that matched fewer than mm slots leaves the ranking here, like a filtered one below (a tile without
+    // a scored posting holds zeros only, and its counts were never cleared)
+    if constexpr (MM) {
+        if (cleared && mm > 1u) {                               // (uniform)
+#pragma unroll
+            for (int j = 0; j < E; j++) {
+                const u32 e = j * THREADS + tid;
+                if ((u32)mc[e] < mm) acc[e] = 0.f;
+            }
+            __syncthreads();
+        }
+    }
     // the batch's document filter: the scores of the non-eligible docs are cleared BEFORE any selection, so that no excluded doc
     // ever raises a slot, a histogram bin or the cached bound, or becomes a candidate
     if (p.filt) {                                               // (uniform)
@@ -915,14 +970,18 @@ __device__ __forceinline__ void sa_bm25_tile_item(const Bm25Params& p, const u32
     }   // top-k
 }
 
-template <int TILE, int THREADS, int MODE, bool IMP>
+// MM (minimum-should-match): the match counts, a byte per accumulator and spare slot, lie BEHIND the item's LDS (the MODE 0 selection
+// lists alias the accumulators, not the counts -- which are dead by then anyway)
+template <int TILE, int THREADS, int MODE, bool IMP, bool MM = false>
 __global__ void __launch_bounds__(THREADS) sa_k_bm25_tiles(const Bm25Params p) {
     // grid (queries, tiles): x runs fastest, so the dispatch order is tile-major without a division
-    __shared__ alignas(16) u64 smem[sa_tile_smem_u64<TILE, MODE>()];
+    constexpr size_t ITEM_U64 = sa_tile_smem_u64<TILE, MODE>();
+    __shared__ alignas(16) u64 smem[ITEM_U64 + (MM ? (TILE + SA_WAVE) / 8 : 0)];
     __shared__ float s_tab[sa_tile_tab_floats<THREADS, IMP>()];
     const u32 tile = p.tile0 + blockIdx.z * SA_GRID_Y + blockIdx.y;
     if (tile >= p.tile_end) return;
-    sa_bm25_tile_item<TILE, THREADS, MODE, IMP>(p, tile, blockIdx.x, smem, s_tab);
+    if constexpr (MM) sa_bm25_tile_item<TILE, THREADS, MODE, IMP, true>(p, tile, blockIdx.x, smem, s_tab, (unsigned char*)(smem + ITEM_U64));
+    else sa_bm25_tile_item<TILE, THREADS, MODE, IMP>(p, tile, blockIdx.x, smem, s_tab);
 }
 
 // The queries the sparse candidate path handed back (usually none): their number is only known on the
@@ -1759,6 +1818,15 @@ int sa_launch_make_bounds(sa_index* ix, const u32* d_terms, u32 BT, u32* d_bound
 }
 
 
+#define SA_LAUNCH_TILE_MM(TILE, THREADS)                                                           \
+    {                                                                                              \
+        if (MODE == 1 && p.imp)                                                                    \
+            hipLaunchKernelGGL((sa_k_bm25_tiles<TILE, THREADS, MODE, MODE == 1, true>), grid, dim3(THREADS), 0, st, p); \
+        else                                                                                       \
+            hipLaunchKernelGGL((sa_k_bm25_tiles<TILE, THREADS, MODE, false, true>), grid, dim3(THREADS), 0, st, p); \
+    }                                                                                              \
+    break
+
 #define SA_LAUNCH_TILE(TILE, THREADS)                                                              \
     {                                                                                              \
         if (MODE == 1 && p.imp)                                                                    \
@@ -1773,6 +1841,18 @@ static int sa_launch_bm25_mode(sa_index* ix, const Bm25Params& p, hipStream_t st
     const u32 nt = p.tile_end - p.tile0;
     const u32 gy = nt < SA_GRID_Y ? nt : SA_GRID_Y;
     const dim3 grid(p.nq, gy, (nt + SA_GRID_Y - 1) / SA_GRID_Y);
+    if (p.min_match_off) {                                      // the counting instantiations (sa_min_match_tiles)
+        switch (ix->tile_docs) {
+            case 1024: SA_LAUNCH_TILE_MM(1024, 128);
+            case 2048: SA_LAUNCH_TILE_MM(2048, 64);
+            case 4096: SA_LAUNCH_TILE_MM(4096, 128);
+            case 8192: SA_LAUNCH_TILE_MM(8192, 256);
+            default:
+                sa_set_error("minimum-should-match: no counting kernel for tile_docs %u", ix->tile_docs);
+                return SA_ERR_UNSUPPORTED;
+        }
+        return SA_OK;
+    }
     switch (ix->tile_docs) {
         case 1024: SA_LAUNCH_TILE(1024, 128);
         case 2048: SA_LAUNCH_TILE(2048, 64);
@@ -1795,6 +1875,9 @@ static int sa_launch_bm25_mode(sa_index* ix, const Bm25Params& p, hipStream_t st
             hipLaunchKernelGGL((sa_k_bm25_tiles_list<TILE, THREADS, false>), dim3(grid), dim3(THREADS), 0, st, p); \
     }                                                                                              \
     break
+
+// the tile sizes the counting (minimum-should-match) instantiations of the per-query tile kernel exist for
+bool sa_min_match_tiles(u32 tile_docs) { return tile_docs == 1024 || tile_docs == 2048 || tile_docs == 4096 || tile_docs == 8192; }
 
 int sa_launch_bm25_list(sa_index* ix, const Bm25Params& p, hipStream_t st) {
     if (ix->n_tiles == 0 || p.B == 0) return SA_OK;

@@ -73,14 +73,21 @@ struct Bm25Params {
     const u64* filt;       // one bit per local doc
     const u32* filt_blk;   // [filt_nblk] eligible docs per 1024-doc block
     u32 filt_nblk;
+    // minimum-should-match (sa_batch_set_min_match), or 0: u32[B] per device row -- the number of query slots a doc must match to stay
+    // in the ranking -- lie this many bytes behind `terms` (both are parts of the batch's upload block).  Only the counting
+    // instantiations of sa_k_bm25_tiles read them (p.stats then counts the tiles they skipped)
+    u32 min_match_off;
     // outputs
     float* dense_out;      // [B][n_docs] or null
     u64* cand;             // [B][n_tiles][k] composite keys (global doc ids) or null
 };
+// (min_match_off sits in what was padding: the kernel arguments of every kernel stay where they were)
+static_assert(sizeof(Bm25Params) == 336, "Bm25Params: a new field moves the kernel arguments of every BM25 kernel");
 
 // host launchers of the BM25 kernels (sa_bm25.hip), called by the batch code (sa_batch.hip)
 void sa_fill_params(const sa_index* ix, Bm25Params& p);
 u32 sa_tile_waves(u32 tile_docs);
 int sa_launch_bm25(sa_index* ix, const Bm25Params& p, hipStream_t st);                // per-query tile kernel (p.qlist: rows)
 int sa_launch_bm25_list(sa_index* ix, const Bm25Params& p, hipStream_t st);           // ... over the device's query list
+bool sa_min_match_tiles(u32 tile_docs);                                                // ... has counting instantiations (p.min_match_off) for this tile size
 int sa_launch_bm25_groups(sa_index* ix, const struct sa_batch* bt, const Bm25Params& p, u32 tile0, hipStream_t st);

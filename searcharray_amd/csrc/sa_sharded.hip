@@ -371,6 +371,12 @@ extern "C" int sa_sharded_batch_set_filter(sa_sharded_batch_t* bt, sa_sharded_fi
     return bt->sh->all([&](int g) { return sa_batch_set_filter(bt->parts[(size_t)g], f ? f->parts[(size_t)g] : nullptr); });
 }
 
+// (collective like set_filter; every shard's batch gets the same per-query values)
+extern "C" int sa_sharded_batch_set_min_match(sa_sharded_batch_t* bt, const uint32_t* min_match) {
+    SA_ARG(bt && bt->sh, "null batch");
+    return bt->sh->all([&](int g) { return sa_batch_set_min_match(bt->parts[(size_t)g], min_match); });
+}
+
 extern "C" int sa_sharded_batch_destroy(sa_sharded_batch_t* bt) {
     if (!bt) return SA_OK;
     if (bt->sh) {

@@ -389,11 +389,19 @@ class DeviceIndex(_options.OptionsMixin):
         return ms.value, ab.value
 
     def batch(self, queries: np.ndarray, k: int = 10, k1: float = 1.2, b: float = 0.75,
-              idf: Optional[np.ndarray] = None, opts=None, filter: Optional["DocFilter"] = None) -> "QueryBatch":
-        """a resident top-k batch; ``filter``: a ``DocFilter`` of this index the batch ranks inside (``QueryBatch.set_filter``)"""
+              idf: Optional[np.ndarray] = None, opts=None, filter: Optional["DocFilter"] = None, min_match=None) -> "QueryBatch":
+        """a resident top-k batch; ``filter``: a ``DocFilter`` of this index the batch ranks inside (``QueryBatch.set_filter``);
+        ``min_match``: per query, the number of query slots a doc must match (``QueryBatch.set_min_match``)"""
+        mm = None if min_match is None else min_match_values(min_match, np.asarray(queries).shape[0] if np.ndim(queries) == 2 else -1)
         bt = QueryBatch(self, queries, k=k, k1=k1, b=b, idf=idf, opts=opts)
-        if filter is not None:
-            bt.set_filter(filter)
+        try:
+            if filter is not None:
+                bt.set_filter(filter)
+            if mm is not None:
+                bt.set_min_match(mm)
+        except Exception:
+            bt.close()
+            raise
         return bt
 
     def doc_filter(self, rows=None, mask=None) -> "DocFilter":
@@ -528,6 +536,18 @@ class DocFilter:
             pass
 
 
+def min_match_values(values, n_queries: int) -> np.ndarray:
+    """minimum-should-match values of a batch, checked before anything is launched: one non-negative integer per query -> uint32[B]"""
+    a = np.asarray(values)
+    if a.ndim != 1 or a.dtype.kind not in "iu":
+        raise ValueError("min_match takes a 1-d sequence of integers, one per query")
+    if n_queries >= 0 and a.shape[0] != n_queries:
+        raise ValueError(f"min_match needs one entry per query ({n_queries}), got {a.shape[0]}")
+    if a.size and int(a.min()) < 0:
+        raise ValueError("min_match entries must be >= 0")
+    return np.ascontiguousarray(np.minimum(a, 0xFFFFFFFF), dtype=np.uint32)
+
+
 class QueryBatch(_options.OptionsMixin):
     _opt_setter = "sa_batch_set_options"
 
@@ -586,6 +606,18 @@ class QueryBatch(_options.OptionsMixin):
             raise TypeError("set_filter takes a DocFilter or None")
         self._call("sa_batch_set_filter", self._h, filter._need() if filter is not None else None)
 
+    def set_min_match(self, values):
+        """Minimum-should-match (Solr ``mm``): query i keeps only the docs that match at least ``values[i]`` of its query slots, every
+        other doc scores 0; ``None`` clears the values.  A slot matches a doc when its own contribution is > 0, slots count separately,
+        padding and unknown terms never match; values <= 1 are the plain disjunction.  Applies from the next run on, persists across
+        ``reset`` / ``step`` (row i of every later query set gets value i) like a filter; such a batch runs on the per-query tile
+        kernels (``last_route()`` says 'exhaustive') and ``seeds()`` is all zero (``sa_batch_set_min_match``)."""
+        if values is None:
+            self._call("sa_batch_set_min_match", self._h, None)
+            return
+        mm = min_match_values(values, self.B)
+        self._call("sa_batch_set_min_match", self._h, p_u32(mm))
+
     def run(self, sync: bool = True):
         self._call("sa_batch_run", self._h, 1 if sync else 0)
 
@@ -622,6 +654,12 @@ class QueryBatch(_options.OptionsMixin):
         out = ctypes.c_int(0)
         self._call("sa_batch_last_route", self._h, ctypes.byref(out))
         return {0: "exhaustive", 1: "pruned", 2: "staged"}[out.value]
+
+    def row_order(self) -> np.ndarray:
+        """the caller query each device row of the current set holds (sa_batch_row_order), uint32[B]; diagnostics only (tests)"""
+        out = np.zeros(self.B, dtype=np.uint32)
+        self._call("sa_batch_row_order", self._h, p_u32(out))
+        return out
 
     def seeds(self) -> np.ndarray:
         """the bound every query of the current set starts with (sa_batch_seeds), float32[B], 0 = none"""

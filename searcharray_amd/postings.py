@@ -717,7 +717,8 @@ class SearchArray(ExtensionArray):
         return "\n".join("        " + ln for ln in lines) + "\n"
 
     # -- batched top-k (no counterpart in the reference: its callers loop over score() + argpartition)
-    def search(self, queries, k: int = 10, similarity=default_bm25, devices=None, filter=None) -> Tuple[np.ndarray, np.ndarray]:
+    def search(self, queries, k: int = 10, similarity=default_bm25, devices=None, filter=None, mm=None,
+               q_op: str = "OR") -> Tuple[np.ndarray, np.ndarray]:
         """Top-``k`` docs for many queries at once, without materialising dense score vectors:
         ``queries`` is a list of token lists (each scored as a disjunction: the sum of its terms' BM25,
         ``np.sum([arr.score(t) for t in q], axis=0)`` in reference terms) or a list of strings (each run
@@ -731,8 +732,39 @@ class SearchArray(ExtensionArray):
         row ids, or a reusable filter from :meth:`doc_filter` / :meth:`term_filter`.  The result is the top-``k`` of the unfiltered
         scores with the excluded rows' scores set to 0: idf, average doc length and corpus size stay those of the WHOLE array.
         This is not the reference's slice semantics -- ``arr[rows].score(...)`` recomputes docfreq inside the slice --, and
-        ``arr[rows].search(...)`` keeps raising."""
-        return self._topk(queries, k, similarity, phrases=False, devices=devices, filter=filter)
+        ``arr[rows].search(...)`` keeps raising.
+        ``mm``: Solr's minimum-should-match, per query -- an int, a spec string (``"2"``, ``"-1"``, ``"75%"``, ``"2<75%"``) or a
+        sequence with one such entry per query, each resolved against the number of the query's tokens (unknown tokens count as
+        clauses, as in ``edismax``).  A row that matches fewer of the query's tokens scores 0; a token given twice counts twice.
+        ``q_op="AND"`` requires all of them (``mm="100%"``, whatever ``mm`` says, as in ``edismax``).  Scores do not change, and
+        a ``filter`` applies as well."""
+        return self._topk(queries, k, similarity, phrases=False, devices=devices, filter=filter, mm=mm, q_op=q_op)
+
+    @staticmethod
+    def _min_match_arg(mm, q_op, n_tokens):
+        """``search(mm=, q_op=)``, checked and resolved per query: None (a plain disjunction) or one integer per query"""
+        if q_op not in ("OR", "AND"):
+            raise ValueError("q_op must be 'OR' or 'AND'")
+        B = len(n_tokens)
+        if q_op == "AND":
+            specs = ["100%"] * B
+        elif mm is None:
+            return None
+        elif isinstance(mm, (str, numbers.Integral)) and not isinstance(mm, bool):
+            specs = [mm] * B
+        else:
+            if not is_list_like(mm):
+                raise ValueError("mm: an integer, a Solr mm spec string, or a sequence with one of them per query")
+            specs = list(mm)
+            if len(specs) != B:
+                raise ValueError(f"mm needs one entry per query ({B}), got {len(specs)}")
+        from .solr import parse_min_should_match
+        out = np.zeros(B, dtype=np.int64)
+        for i, (spec, n) in enumerate(zip(specs, n_tokens)):
+            if isinstance(spec, bool) or not isinstance(spec, (str, numbers.Integral)):
+                raise ValueError(f"mm entries are integers or Solr mm spec strings, got {spec!r}")
+            out[i] = parse_min_should_match(n, str(int(spec)) if isinstance(spec, numbers.Integral) else spec)
+        return out
 
     def _filter_arg(self, f):
         """a mask / row-id filter argument, checked: (mask, None) or (None, rows)"""
@@ -772,7 +804,7 @@ class SearchArray(ExtensionArray):
         value or one per phrase).  Any phrase ``score`` takes is fine -- repeated tokens, long phrases, slop."""
         return self._topk(phrases, k, similarity, phrases=True, devices=devices, slop=slop)
 
-    def _topk(self, queries, k, similarity, phrases, devices=None, slop=0, filter=None):
+    def _topk(self, queries, k, similarity, phrases, devices=None, slop=0, filter=None, mm=None, q_op="OR"):
         if getattr(similarity, "kind", None) != "bm25":
             raise ValueError("batched search needs a stock BM25 similarity (bm25_similarity(k1, b))")
         if self._rows is not None:
@@ -784,6 +816,7 @@ class SearchArray(ExtensionArray):
         fmask = frows = None
         if filter is not None and not isinstance(filter, (DocFilter, ShardedDocFilter)):
             fmask, frows = self._filter_arg(filter)                 # (checked before anything is launched)
+        need = None if phrases else self._min_match_arg(mm, q_op, [len(q) for q in toks])
         if B == 0 or len(self._core.doc_lens) == 0:
             return np.zeros((B, k), np.float32), np.full((B, k), NO_DOC, np.uint64)
         # (an explicit device list is honoured even when it names ONE device: a one-shard handle on that GPU)
@@ -800,6 +833,8 @@ class SearchArray(ExtensionArray):
             batch = dev.batch(mat, k=k, k1=similarity.k1, b=similarity.b)
         own = None
         try:
+            if need is not None and int(need.max()) > 1:
+                batch.set_min_match(need)
             if filter is not None:
                 sharded = devices is not None and len(devices) >= 1
                 if isinstance(filter, ShardedDocFilter) or (isinstance(filter, DocFilter) and not sharded):

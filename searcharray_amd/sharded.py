@@ -24,7 +24,7 @@ import numpy as np
 from . import _lib
 from . import options as _options
 from . import roaringish as rz
-from .device_index import NO_TERM, DeviceIndex, compute_idf
+from .device_index import NO_TERM, DeviceIndex, compute_idf, min_match_values
 
 
 def split_by_doc_range(words: np.ndarray, term_off: np.ndarray, bounds: Sequence[int]):
@@ -167,10 +167,11 @@ class ShardedIndex:
         return ShardedDocFilter(self, h)
 
     def batch(self, queries: np.ndarray, k: int = 10, k1: float = 1.2, b: float = 0.75, opts=None,
-              filter: Optional["ShardedDocFilter"] = None) -> "ShardedBatch":
+              filter: Optional["ShardedDocFilter"] = None, min_match=None) -> "ShardedBatch":
         q = np.asarray(queries, dtype=np.int64)
         if q.ndim != 2:
             raise ValueError("queries must be [B][T] term ids")
+        mm = None if min_match is None else min_match_values(min_match, q.shape[0])
         idf = _lib.as_f32(self.idfs(q.reshape(-1)).reshape(q.shape))
         terms = _lib.as_u32(np.where((q >= 0) & (q < self.n_terms), q, NO_TERM).astype(np.uint32))
         h = _lib.ctypes.c_void_p()
@@ -178,8 +179,14 @@ class ShardedIndex:
             self.api.call("sa_sharded_batch_create", self._h, _lib.p_u32(terms), _lib.p_f32(idf), q.shape[0], q.shape[1], int(k),
                           np.float32(k1), np.float32(b), _lib.ctypes.byref(h))
         bt = ShardedBatch(self, h, q.shape[0], int(k), n_terms=q.shape[1], opts=_options.Options(self._opts, opts))
-        if filter is not None:
-            bt.set_filter(filter)
+        try:
+            if filter is not None:
+                bt.set_filter(filter)
+            if mm is not None:
+                bt.set_min_match(mm)
+        except Exception:
+            bt.close()
+            raise
         return bt
 
     def phrase_batch(self, phrases, k: int = 10, k1: float = 1.2, b: float = 0.75, slop=0, opts=None) -> "ShardedBatch":
@@ -275,6 +282,16 @@ class ShardedBatch(_options.OptionsMixin):
         if filter is not None and not isinstance(filter, ShardedDocFilter):
             raise TypeError("set_filter takes a filter of ShardedIndex.doc_filter or None")
         self._call("sa_sharded_batch_set_filter", self._h, filter._need() if filter is not None else None)
+
+    def set_min_match(self, values):
+        """minimum-should-match, the same per-query values on every shard's batch (``QueryBatch.set_min_match``); ``None`` clears them"""
+        if values is None:
+            self._call("sa_sharded_batch_set_min_match", self._h, None)
+            return
+        if self.T is None:
+            raise ValueError("phrase batches do not take minimum-should-match")
+        mm = min_match_values(values, self.B)
+        self._call("sa_sharded_batch_set_min_match", self._h, _lib.p_u32(mm))
 
     def run(self, sync: bool = True):
         self._call("sa_sharded_batch_run", self._h, 1 if sync else 0)

@@ -113,6 +113,7 @@ typedef struct sa_options {
     int64_t io_piece_bytes;  /* bytes per staged piece */
     int64_t io_threads;      /* file threads */
     int64_t trace;           /* 1: route decisions to stderr */
+    int64_t stage_pipe;      /* staged-tile route: the next tile's layout built while the stage loads are in flight: 1 wherever eligible, 0 never; unset: where eligible from 256 staged terms on */
 } sa_options_t;
 void sa_options_init(sa_options_t* opts);                                  /* all unset */
 int sa_options_set(sa_options_t* opts, const char* name, int64_t value);

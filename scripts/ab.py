@@ -19,7 +19,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from searcharray_amd import synth, _lib                                     # noqa: E402
+from searcharray_amd import synth, _lib, options as sa_options              # noqa: E402
 from searcharray_amd.device_index import DeviceIndex, QueryBatch, compute_idf   # noqa: E402
 
 KEYS = ("SA_GROUP",  "SA_GROUP_WARM", "SA_GROUP_MIN", "SA_GROUP_LOOSE", "SA_GROUP_SIDE", "SA_SPARSE", "SA_GRP_VARIANT",
@@ -38,6 +38,7 @@ def main():
     ap.add_argument("--envs", default="SA_SPARSE=0", help="';'-separated configurations of ','-separated NAME=VALUE")
     ap.add_argument("--qsets", default="baseline")
     ap.add_argument("--queries", type=int, default=256)
+    ap.add_argument("--reps", type=int, default=1, help="repetitions of the whole grid, the libraries ALTERNATING inside each (every library keeps its index)")
     args = ap.parse_args()
     D, V = args.docs, args.vocab
     cpath = os.path.join(args.corpus_cache, f"zipf_{D}_{V}_0_{D}.npz") if args.corpus_cache else ""
@@ -60,11 +61,14 @@ def main():
     qsets = {k_: v for k_, v in qsets.items() if k_ in args.qsets.split(",") and v is not None}
     envs = [dict(kv.split("=") for kv in cfg.split(",") if kv) for cfg in args.envs.split(";")]
     ref = {}
+    loaded = []
     for lib in args.libs.split(","):
         path = lib if os.path.isabs(lib) else os.path.join(ROOT, lib)
         api = _lib.bind(ctypes.CDLL(path), path, allow_missing=True)         # (an older build lacks the newer entry points)
-        index = DeviceIndex(corpus.words, corpus.term_off, corpus.doc_lens, tile_docs=args.tile, api=api)
+        loaded.append((lib, api, DeviceIndex(corpus.words, corpus.term_off, corpus.doc_lens, tile_docs=args.tile, api=api)))
+    for rep, (lib, api, index) in [(r, x) for r in range(args.reps) for x in loaded]:
         df = index.docfreqs()
+        known = set(sa_options.names(api))
         for qname, queries in qsets.items():
             idf = np.asarray([[compute_idf(D, np.asarray([df[t]])) for t in q] for q in queries], dtype=np.float32)
             for k in [int(x) for x in args.ks.split(",")]:
@@ -77,6 +81,8 @@ def main():
                     os.environ.update(cfg)
                     # (configuration "default=1": no route option at all -- the library's own rule picks the route)
                     bopts = {kk: vv for kk, vv in cfg.items() if kk != "default"} if "default" in cfg else dict({"sparse": 0}, **cfg)
+                    dropped = sorted(kk for kk in bopts if sa_options._norm(kk) not in known)       # (an older build: a switch it does not have is what it always does)
+                    bopts = {kk: vv for kk, vv in bopts.items() if kk not in dropped}
                     batch = QueryBatch(index, queries, k=k, idf=idf, opts=bopts)
                     for _ in range(3):
                         batch.run(sync=False)
@@ -114,15 +120,20 @@ def main():
                         names = ["slice_ends_and_scan", "offsets_and_chunk_list", "barrier_a", "next_tile_reads_and_stage_loads_issued", "stage_loads_landed_and_written", "barrier_b",
                                  "query_phase_and_scan", "barrier_c", "stage_a_tail", "stage_b_rounds_tail", "pass_tail", "tile_top",
                                  "a_search", "a_check", "a_compact", "a_barrier", "b_round_head", "b_lookups", "b_compact", "b_barrier", "before_flush", "flush_atomics_append", "flush_refresh_and_barriers", "flush_probes_and_score"]
+                        # (round 7, behind the counts: the next tile's layout built in the load shadow; the explicit wait for the stage loads --
+                        #  with it, "stage_loads_landed_and_written" is the LDS writes alone.  Zero in a round-6 probe build.)
+                        cycles = {nm: round(v[i] / passes, 1) for i, nm in enumerate(names)}
+                        cycles.update({"prepare_next_tile": round(v[29] / passes, 1), "stage_loads_wait": round(v[30] / passes, 1)})
                         probe = {"tile_passes": v[24], "workgroups": v[26], "candidates_per_pass": round(v[25] / passes, 1), "finalists_per_pass": round(v[27] / passes, 1), "flushes_per_pass": round(v[28] / passes, 2),
-                                 "cycles_per_pass": {nm: round(v[i] / passes, 1) for i, nm in enumerate(names)},
-                                 "cycles_per_pass_total": round(sum(v[:24]) / passes, 1),
+                                 "cycles_per_pass": cycles,
+                                 "cycles_per_pass_total": round((sum(v[:24]) + v[29] + v[30]) / passes, 1),
                                  "note": "s_memtime of wave 0 at the phase boundaries (shader cycles); one launch"}
                     r0 = ref.setdefault((qname, k), res)
                     same = bool(np.array_equal(r0[0], res[0]) and np.array_equal(r0[1], res[1]))
-                    print(json.dumps({"lib": os.path.basename(lib), "queries": qname, "k": k, "docs": D, **cfg,
+                    print(json.dumps({"lib": os.path.basename(lib), **({"rep": rep} if args.reps > 1 else {}), "queries": qname, "k": k, "docs": D, **cfg, **({"not_in_this_build": dropped} if dropped else {}),
                                       "route": batch.last_route(), "ms_per_step": round(dt * 1e3, 4), "kernel_ms": round(kms, 4), "same_results": same, **({"probe": probe} if probe else {})}), flush=True)
                     batch.close()
+    for _, _, index in loaded:
         index.close()
 
 

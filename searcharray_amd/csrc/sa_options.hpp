@@ -72,7 +72,9 @@
     X(io_piece_bytes)  /* bytes per staged piece */                                                                                \
     X(io_threads)      /* file threads */                                                                                          \
     /* ---- diagnostics */                                                                                                         \
-    X(trace)           /* 1: route decisions to stderr */
+    X(trace)           /* 1: route decisions to stderr */                                                                           \
+    /* ---- appended (the struct is versioned by its size: new fields go last) */                                                  \
+    X(stage_pipe)      /* staged-tile route: the next tile's layout built while the stage loads are in flight: 1 wherever eligible, 0 never; unset: where eligible from 256 staged terms on */
 
 struct sa_options_fields {
     uint64_t struct_size;

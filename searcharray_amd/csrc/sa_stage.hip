@@ -570,20 +570,29 @@ __device__ __forceinline__ u32 sa_st_wave_incl_scan(u32 v) {
 // Block-wide exclusive scan of TWO u32 per thread behind ONE barrier: the waves' totals go to the half of `red` (2 x 2 NWAVES
 // words) that `parity` selects; the caller alternates the parity from call to call, so a wave that is still reading one half
 // cannot see the next call's totals (two calls apart there is a barrier every wave has passed).
+// Behind the barrier every wave scans the NWAVES totals ACROSS ITS LANES (lane l holds wave l & 7's pair: three DPP steps inside a row)
+// and takes its own offset and the block's totals out with readlane -- a dozen vector instructions.  (Summing the totals wave by wave
+// under `w < wave_id` was one select per total through eight scalar mask pairs that lived -- spilled -- across the whole kernel.)
 template <int NWAVES>
 __device__ __forceinline__ void sa_block_excl_scan2(u32 a, u32 b, u32* red, u32 parity, u32& ea, u32& eb, u32& ta, u32& tb) {
+    static_assert(NWAVES == 8, "the totals of eight waves: one half of a DPP row");
     const u32 ia = sa_st_wave_incl_scan(a), ib = sa_st_wave_incl_scan(b);
     u32* const r = red + parity * (2u * NWAVES);
     if (sa_lane() == SA_WAVE - 1) { r[2 * sa_wave_id()] = ia; r[2 * sa_wave_id() + 1] = ib; }
     __syncthreads();
-    u32 ba = 0, bb = 0; ta = 0; tb = 0;
-#pragma unroll
-    for (int w = 0; w < NWAVES; w++) {
-        const u32 sa = r[2 * w], sb = r[2 * w + 1];
-        if (w < sa_wave_id()) { ba += sa; bb += sb; }
-        ta += sa; tb += sb;
-    }
-    ea = ba + ia - a; eb = bb + ib - b;
+    const u32 l = (u32)sa_lane() & (u32)(NWAVES - 1);
+    const u32 sa = r[2u * l], sb = r[2u * l + 1u];
+    u32 xa = sa, xb = sb;
+    xa += (u32)__builtin_amdgcn_update_dpp(0, (int)xa, SA_DPP_ROW_SHR(1), 0xf, 0xf, false);
+    xb += (u32)__builtin_amdgcn_update_dpp(0, (int)xb, SA_DPP_ROW_SHR(1), 0xf, 0xf, false);
+    xa += (u32)__builtin_amdgcn_update_dpp(0, (int)xa, SA_DPP_ROW_SHR(2), 0xf, 0xf, false);
+    xb += (u32)__builtin_amdgcn_update_dpp(0, (int)xb, SA_DPP_ROW_SHR(2), 0xf, 0xf, false);
+    xa += (u32)__builtin_amdgcn_update_dpp(0, (int)xa, SA_DPP_ROW_SHR(4), 0xf, 0xf, false);
+    xb += (u32)__builtin_amdgcn_update_dpp(0, (int)xb, SA_DPP_ROW_SHR(4), 0xf, 0xf, false);     // (lanes 0 .. 7: inclusive sums over the waves 0 .. l)
+    const int w = __builtin_amdgcn_readfirstlane(sa_wave_id());
+    ta = (u32)__builtin_amdgcn_readlane((int)xa, NWAVES - 1); tb = (u32)__builtin_amdgcn_readlane((int)xb, NWAVES - 1);
+    ea = (u32)__builtin_amdgcn_readlane((int)(xa - sa), w) + ia - a;
+    eb = (u32)__builtin_amdgcn_readlane((int)(xb - sb), w) + ib - b;
 }
 
 // -DSA_PROBE (scripts/build_probe.sh; never in the product build): cycles a workgroup spends per phase of a tile pass, summed
@@ -601,6 +610,14 @@ extern "C" int sa_debug_stage_probe_read(unsigned long long* out16, int clear) {
 #define SA_SPT(i) do { } while (0)
 #endif
 
+// the compiler forgets what it knows about x: an LDS address formed from it is computed where it is used, not hoisted out of the
+// tile loop and kept (spilled) across it -- a scratch reload is a vector-memory op and would wait behind the stage loads in flight
+#ifdef SA_EMU
+#define SA_ST_OPAQUE(x) do { } while (0)
+#else
+#define SA_ST_OPAQUE(x) asm volatile("" : "+v"(x))
+#endif
+
 typedef unsigned int sa_v2u __attribute__((vector_size(8)));
 typedef unsigned int sa_v4u __attribute__((vector_size(16)));
 struct alignas(8) StChunk { u32 dc, off; };    // a copy chunk: first stage cell | postings (1 .. 8) << 13; byte offset of its first posting from the stream base
@@ -610,7 +627,14 @@ struct alignas(8) StChunk { u32 dc, off; };    // a copy chunk: first stage cell
 // next to the presence bitmaps, and a candidate's bit is part of stage A's test: an excluded doc never becomes a survivor, so it never
 // reaches a histogram or a candidate list.  A tile without an eligible doc is passed over before its chunk list, its stage loads and
 // its query phase (its cursors and read-ahead move on as usual).  The unfiltered instantiations contain none of it.
-template <int TMAX, int KT, bool FILT>
+// PIPE (KT = 1, every staged term with a directory row: sa_launch_stage): the tile loop is PIPELINED by one tile.  The layout of a tile
+// -- slice sizes and bounds from the directory words, the block scan, stage offsets, the chunk list -- depends on nothing but words the
+// thread holds a tile ahead, so pass i builds tile i + 1's while its own stage loads are in flight, into the OTHER half of a double-
+// buffered s_off / s_tmax (the probed terms' entries live in both halves: one index serves either) and into s_cd (which pass i has
+// finished reading: the barrier of the preparation's scan lies between).  A pass that finds its layout prepared starts by issuing its
+// loads.  A pass that does not -- a workgroup's first tile, a tile behind one that did not fit the stage or had more chunks than one
+// round of loads takes, FILT: behind a tile without an eligible doc -- builds it in place, like the un-pipelined loop does every time.
+template <int TMAX, int KT, bool FILT, bool PIPE>
 __global__ void __launch_bounds__(SA_ST_NT, 4) sa_k_bm25_stage(const StageParams sp) {
     constexpr int CAP = SaStCap<TMAX>::v;
     constexpr int NT = SA_ST_NT, NW = NT / SA_WAVE;
@@ -619,13 +643,15 @@ __global__ void __launch_bounds__(SA_ST_NT, 4) sa_k_bm25_stage(const StageParams
     constexpr int NWL = 1024;                                    // candidates per round of stage A (its survivors fit s_b)
     constexpr int KB = 8;                                        // chunk loads a lane issues before it waits
     static_assert(KT == 1 || KT == 2, "one or two staged terms per thread");
+    static_assert(!PIPE || KT == 1, "the pipelined loop: one staged term per thread (two leave no LDS for the second half)");
+    constexpr u32 HALF = SA_ST_UMAX;                             // PIPE: entries per half of s_off / s_tmax
     static_assert(SA_ST_UMAX <= CAP, "a single document's postings must fit the stage");
     static_assert(CAP <= 8192 && SA_ST_UMAX <= 1024, "13-bit stage cells in a chunk descriptor");
     static_assert(SA_ST_BMAX <= 256 && TMAX <= 8, "8-bit query, 3-bit position in a work-list record");
     __shared__ alignas(16) u64 s_post[CAP];                      // the stage: every staged term's slice of this tile, doc-sorted
-    __shared__ u32 s_off[SA_ST_UMAX];                           // per distinct term: first cell << 16 | postings; a probed term: probe row << 16 | SA_ST_PROBE
-    __shared__ u32 s_tmax[SA_ST_UMAX];                          // bound (fp32 pattern) of its factors in this tile
-    __shared__ StChunk s_cd[NCH];                               // the copy's chunk list; then the candidate work list (u32 records)
+    __shared__ u32 s_off[(PIPE ? 2 : 1) * SA_ST_UMAX];          // per distinct term: first cell << 16 | postings; a probed term: probe row << 16 | SA_ST_PROBE (PIPE: two halves, tiles alternate)
+    __shared__ unsigned short s_tmax[(PIPE ? 2 : 1) * SA_ST_UMAX];  // bound of its factors in this tile: the UPPER 16 bits of the fp32 pattern, rounded up (what a cm word holds)
+    __shared__ StChunk s_cd[NCH];                               // the copy's chunk list (PIPE: of the NEXT tile once this tile's loads are issued)
     __shared__ unsigned short s_pu[SA_ST_BMAX * TMAX];          // [query][position]: distinct-term index (SA_ST_NONE: no term)
     __shared__ alignas(16) float s_pw[SA_ST_BMAX * TMAX];       //   its weight
     __shared__ alignas(16) float s_psfx[SA_ST_BMAX * TMAX];     //   what the positions >= i can add in THIS tile (with the margin)
@@ -649,8 +675,8 @@ __global__ void __launch_bounds__(SA_ST_NT, 4) sa_k_bm25_stage(const StageParams
     auto cell_at = [&](u32 boff) -> u64 { const sa_v2u v = __builtin_amdgcn_raw_buffer_load_b64(r_imp, boff, 0, 0); return ((u64)v[1] << 32) | (u64)v[0]; };
     auto key_at = [&](u32 boff) -> u32 { return __builtin_amdgcn_raw_buffer_load_b32(r_imp, boff + 4u, 0, 0); };      // (the doc key of a cell: its high word)
 #ifdef SA_PROBE
-    u64 pacc[24];
-    for (int i = 0; i < 24; i++) pacc[i] = 0;
+    u64 pacc[26];
+    for (int i = 0; i < 26; i++) pacc[i] = 0;
     u64 plast = __builtin_amdgcn_s_memtime();
     u32 ptiles = 0, pcand = 0, pfin = 0, pflush = 0;
 #endif
@@ -698,7 +724,7 @@ __global__ void __launch_bounds__(SA_ST_NT, 4) sa_k_bm25_stage(const StageParams
         if (u < NS) {
             const StTerm t = sp.terms[u];
             src0[kx] = (u32)(t.cell0 - sp.cell_base);
-            s_tmax[u] = t.maxf;                                 // (a walked term keeps this bound; a term with a row gets its tile's)
+            s_tmax[u] = (unsigned short)((t.maxf + 0xFFFFu) >> 16);      // (a walked term keeps this bound, rounded up like a cm word; a term with a row gets its tile's)
             if (t.row != SA_ST_NOROW) {
                 rowed[kx] = true;
                 cmi[kx] = t.row * (sp.n_st + 1u) + t_begin;
@@ -718,6 +744,7 @@ __global__ void __launch_bounds__(SA_ST_NT, 4) sa_k_bm25_stage(const StageParams
     if (NS + tid < U) {
         const StTerm t = sp.terms[NS + tid];
         s_off[NS + tid] = (t.probe << 16) | SA_ST_PROBE;
+        if constexpr (PIPE) s_off[HALF + NS + tid] = (t.probe << 16) | SA_ST_PROBE;
         pcmi = t.row * (sp.n_st + 1u) + t_begin;
         pnx = __builtin_amdgcn_raw_buffer_load_b32(r_dir, (pcmi << 3) + 4u, 0, 0);
     }
@@ -824,7 +851,16 @@ __global__ void __launch_bounds__(SA_ST_NT, 4) sa_k_bm25_stage(const StageParams
     u32 fw_next = 0u;
     if constexpr (FILT) fw_next = lane < fwn ? sp.filt[(u32)(((u64)t_begin * sp.docs) >> 5) + lane] : 0u;
 
+    // PIPE (all block-uniform): hcur = the half of s_off / s_tmax that holds the current tile's layout; prepared = the previous pass
+    // built it (NC_nx: its chunks); reload = the previous pass consumed this tile's directory words and then found the tile too big
+    // for the stage -- the words are read again and the pass builds its layout in place, in doc sub-ranges
+    u32 hcur = 0u, NC_nx = 0u;
+    bool prepared = false, reload = false;
     for (u32 tile = t_begin; tile < t_end; tile += t_step) {
+        if constexpr (PIPE) hcur = (u32)__builtin_amdgcn_readfirstlane((int)hcur);      // (a scalar: the halves' bases stay out of the vector registers)
+        u32* const off_c = s_off + hcur * HALF;
+        unsigned short* const tmx_c = s_tmax + hcur * HALF;
+        const bool fresh = !PIPE || !prepared;                   // this pass builds the tile's layout itself
         const u64 tile_d0 = (u64)tile * sp.docs;
         const u64 tile_d1 = tile_d0 + sp.docs < sp.n_docs ? tile_d0 + sp.docs : sp.n_docs;
         SA_SPT(11);
@@ -838,13 +874,23 @@ __global__ void __launch_bounds__(SA_ST_NT, 4) sa_k_bm25_stage(const StageParams
         }
         // postings of this thread's terms in this tile and the bound of their factors there, from what was read a tile ago
         u32 n_t[KT], tm[KT];
-        {
+        if constexpr (PIPE) {
+            if (reload) {                                       // (uniform, rare: an oversize tile)
+                const u32 back = tile + t_step < t_end ? t_step : 0u;      // (the entries moved on to the next tile's, if there is one)
+                const sa_v2u e = __builtin_amdgcn_raw_buffer_load_b64(r_dir, rowed[0] ? (cmi[0] - back) << 3 : 0xFFFFFFF0u, 0, 0);
+                ab[0] = e[0]; nx[0] = e[1];
+                pnx = __builtin_amdgcn_raw_buffer_load_b32(r_dir, NS + tid < U ? ((pcmi - back) << 3) + 4u : 0xFFFFFFF0u, 0, 0);
+            }
+        }
+#pragma unroll
+        for (int kx = 0; kx < KT; kx++) { n_t[kx] = 0u; tm[kx] = 0u; }
+        if (fresh) {
             const u32 key = (u32)tile_d1 << 2;
 #pragma unroll
             for (int kx = 0; kx < KT; kx++) {
                 const u32 cmw = nx[kx];
                 u32 nw = 0;
-                if (!rowed[kx] && cmw < key) {
+                if (!PIPE && !rowed[kx] && cmw < key) {
                     nw = 1;
                     if (w1[kx] < key) { nw = 2; while (key_at((src0[kx] + lo[kx] + nw) << 3) < key) nw++; }   // (three postings of a rare term in one tile: hardly ever)
                 }
@@ -854,11 +900,12 @@ __global__ void __launch_bounds__(SA_ST_NT, 4) sa_k_bm25_stage(const StageParams
             }
         }
         const u32 ptm = pnx & 0xFFFF0000u;
-        if (tile + t_step < t_end) {                              // (uniform) the directory entries the passes below read are the next tile's
+        if (fresh && !(PIPE && reload) && tile + t_step < t_end) {     // (uniform) the directory entries the passes below read are the next tile's
 #pragma unroll
             for (int kx = 0; kx < KT; kx++) cmi[kx] += rowed[kx] ? t_step : 0u;
             pcmi += NS + tid < U ? t_step : 0u;
         }
+        if constexpr (PIPE) reload = false;
         // the queries' bounds (a bound only ever rises: a stale one is valid), read a tile ago
         const u32 g_now = g_raw > seed ? g_raw : seed;
         // A tile whose postings do not fit the stage is taken in doc sub-ranges: halve the range until it fits (a single
@@ -889,13 +936,22 @@ __global__ void __launch_bounds__(SA_ST_NT, 4) sa_k_bm25_stage(const StageParams
                     break;
                 }
             }
-            u32 excl, exch, P, NC;
+            u32 excl = 0u, exch = 0u, P = 0u, NC = NC_nx;
+            if (fresh) {                                        // (uniform; PIPE: up to the barrier below)
+            if constexpr (PIPE) {
+                // the next tile's directory words: issued here, landed behind the layout work (in the pipelined passes the
+                // preparation issues them)
+                const sa_v2u e = __builtin_amdgcn_raw_buffer_load_b64(r_dir, rowed[0] ? cmi[0] << 3 : 0xFFFFFFF0u, 0, 0);
+                ab[0] = e[0]; nx[0] = e[1];
+                pnx = __builtin_amdgcn_raw_buffer_load_b32(r_dir, NS + tid < U ? (pcmi << 3) + 4u : 0xFFFFFFF0u, 0, 0);
+            }
             {
                 u32 mine = 0, mch = 0;
 #pragma unroll
                 for (int kx = 0; kx < KT; kx++) { mine += n[kx]; mch += (n[kx] + 7u) >> 3; }
                 sa_block_excl_scan2<NW>(mine, mch, s_red, parity, excl, exch, P, NC);
                 parity ^= 1u;
+                if constexpr (PIPE) P = (u32)__builtin_amdgcn_readfirstlane((int)P);        // (the same in every lane: the sub-range loop's bounds stay scalar)
             }
             // (the rare case apart from the common path: a loop with loads in it makes the compiler wait for every load in flight at its head)
             if (P > (u32)CAP && d_e - d_s > 1ull) {
@@ -914,6 +970,7 @@ __global__ void __launch_bounds__(SA_ST_NT, 4) sa_k_bm25_stage(const StageParams
                     for (int kx = 0; kx < KT; kx++) { mine += n[kx]; mch += (n[kx] + 7u) >> 3; }
                     sa_block_excl_scan2<NW>(mine, mch, s_red, parity, excl, exch, P, NC);
                     parity ^= 1u;
+                    if constexpr (PIPE) P = (u32)__builtin_amdgcn_readfirstlane((int)P);
                 } while (P > (u32)CAP && d_e - d_s > 1ull);
             }
             SA_SPT(0);
@@ -924,9 +981,9 @@ __global__ void __launch_bounds__(SA_ST_NT, 4) sa_k_bm25_stage(const StageParams
                 for (int kx = 0; kx < KT; kx++) {
                     const u32 u = tid + (u32)kx * NT;
                     if (u < NS) {
-                        if (rowed[kx]) s_tmax[u] = tm[kx];
+                        if (rowed[kx]) tmx_c[u] = (unsigned short)(tm[kx] >> 16);
                         {
-                            s_off[u] = (o << 16) | n[kx];
+                            off_c[u] = (o << 16) | n[kx];
                             u32 boff = (src0[kx] + lo[kx]) << 3;
                             for (u32 left = n[kx]; left; ) {
                                 const u32 c = left < 8u ? left : 8u;
@@ -938,10 +995,12 @@ __global__ void __launch_bounds__(SA_ST_NT, 4) sa_k_bm25_stage(const StageParams
                     }
                 }
             }
-            if (NS + tid < U) s_tmax[NS + tid] = ptm;
+            if (NS + tid < U) tmx_c[NS + tid] = (unsigned short)(ptm >> 16);
             SA_SPT(1);
             __syncthreads();
             SA_SPT(2);
+            }
+            if constexpr (PIPE) NC = (u32)__builtin_amdgcn_readfirstlane((int)NC);      // (the same in every lane)
             // ---- the reads for the NEXT tile: cm words, the walked terms' next doc keys, the queries' bounds.  Every load is
             //      UNCONDITIONAL and its result is only looked at a tile later (a load inside a branch makes the compiler wait for
             //      everything in flight where the branch joins); a lane without the case passes an offset past the buffer's end
@@ -949,6 +1008,7 @@ __global__ void __launch_bounds__(SA_ST_NT, 4) sa_k_bm25_stage(const StageParams
             //      those have -- the loops further down contain (rare) loads, and at the head of such a loop the compiler waits
             //      for every load in flight.
             {
+                if constexpr (!PIPE) {
 #pragma unroll
                 for (int kx = 0; kx < KT; kx++) {
                     const u32 kb = rowed[kx] ? 0xFFFFFFE0u : (src0[kx] + lo[kx] + (n_t[kx] - used[kx])) << 3;     // (the cell behind the tile's last posting, whatever the pass)
@@ -959,6 +1019,7 @@ __global__ void __launch_bounds__(SA_ST_NT, 4) sa_k_bm25_stage(const StageParams
                     w1[kx] = key_at(kb + 8u);
                 }
                 pnx = __builtin_amdgcn_raw_buffer_load_b32(r_dir, NS + tid < U ? (pcmi << 3) + 4u : 0xFFFFFFF0u, 0, 0);
+                }
                 g_raw = __hip_atomic_load(&sp.gthr[hasq ? tid : 0u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
             // ---- stage: eight lanes per chunk (and 16 bytes per lane of the probed terms' presence bitmaps).  A lane issues all its
@@ -979,6 +1040,54 @@ __global__ void __launch_bounds__(SA_ST_NT, 4) sa_k_bm25_stage(const StageParams
                 v[i] = cell_at(ok ? d.off + (sub << 3) : 0xFFFFFFF0u);
             }
             SA_SPT(3);
+            // ---- PIPE: the NEXT tile's layout, while this tile's loads are in flight -- what the top of a pass does in the un-pipelined
+            //      loop, from the directory words read a pass ago, into the other half of s_off / s_tmax and into s_cd (every wave has
+            //      read its chunk descriptors above: the scan's barrier lies between).  Only behind the LAST doc sub-range of a
+            //      tile, and only when this tile's chunks went out in one round (a further round reads s_cd when the loads land).
+            //      The words are consumed here and the tile after next's are requested into the same registers -- straight-line, no
+            //      load in a branch: a pass that prepares nothing leaves the entries where they are and reads the same words again.
+            //      A next tile that does not fit the stage: nothing is written, and its pass reads its words again.
+            if constexpr (PIPE) {
+                prepared = false;
+                bool want = d_e >= tile_d1 && tile + t_step < t_end && NC <= (u32)(KB * (NT / 8));
+                if constexpr (FILT) want = want && __builtin_amdgcn_ballot_w64(fw_next != 0u) != 0ull;     // (a tile without an eligible doc is passed over by its own pass)
+                const bool own = rowed[0];
+                const u32 cmw = nx[0], first = ab[0], pcw = pnx;
+                {
+                    const u32 adv = want && tile + 2u * t_step < t_end ? t_step : 0u;
+                    cmi[0] += own ? adv : 0u; pcmi += NS + tid < U ? adv : 0u;
+                    const sa_v2u e = __builtin_amdgcn_raw_buffer_load_b64(r_dir, own ? cmi[0] << 3 : 0xFFFFFFF0u, 0, 0);
+                    ab[0] = e[0]; nx[0] = e[1];
+                    pnx = __builtin_amdgcn_raw_buffer_load_b32(r_dir, NS + tid < U ? (pcmi << 3) + 4u : 0xFFFFFFF0u, 0, 0);
+                }
+                if (want) {                                     // (uniform)
+                    const u32 nn = own ? cmw & 0xFFFFu : 0u;
+                    u32 o, oc, Pn, NCn;
+                    sa_block_excl_scan2<NW>(nn, (nn + 7u) >> 3, s_red, parity, o, oc, Pn, NCn);
+                    parity ^= 1u;
+                    Pn = (u32)__builtin_amdgcn_readfirstlane((int)Pn); NCn = (u32)__builtin_amdgcn_readfirstlane((int)NCn);   // (the same in every lane: scalars for the branches and the next pass)
+                    if (Pn <= (u32)CAP) {                       // (uniform)
+                        u32* const off_n = s_off + (hcur ^ 1u) * HALF;
+                        unsigned short* const tmx_n = s_tmax + (hcur ^ 1u) * HALF;
+                        u32 tv = tid;
+                        SA_ST_OPAQUE(tv);
+                        if (own) {
+                            tmx_n[tv] = (unsigned short)(cmw >> 16);
+                            off_n[tv] = (o << 16) | nn;
+                            u32 boff = (src0[0] + first) << 3;
+                            for (u32 left = nn; left; ) {
+                                const u32 c = left < 8u ? left : 8u;
+                                StChunk d; d.dc = o | (c << 13); d.off = boff;
+                                s_cd[oc] = d;
+                                o += c; oc++; boff += 64u; left -= c;
+                            }
+                        }
+                        if (NS + tid < U) tmx_n[NS + tv] = (unsigned short)(pcw >> 16);
+                        prepared = true; NC_nx = NCn;
+                    } else reload = true;
+                }
+                SA_SPT(24);
+            }
             // ---- the queries: bound; what every position can add at most in THIS tile (weight x bound of the term's factors here);
             //      essential positions; their postings are the candidates.  (Branch-free, the LDS reads in batches: a read inside a
             //      branch is waited for on the spot.)
@@ -992,7 +1101,7 @@ __global__ void __launch_bounds__(SA_ST_NT, 4) sa_k_bm25_stage(const StageParams
 #pragma unroll
                 for (int i = 0; i < TMAX; i++) { const u32 u = s_pu[qb + (u32)i]; have[i] = u != SA_ST_NONE; uu[i] = have[i] ? u : 0u; }
 #pragma unroll
-                for (int i = 0; i < TMAX; i++) { pk[i] = s_off[uu[i]]; ubv[i] = __fmul_rn(__uint_as_float(s_tmax[uu[i]]), s_pw[qb + (u32)i]); }
+                for (int i = 0; i < TMAX; i++) { pk[i] = off_c[uu[i]]; ubv[i] = __fmul_rn(__uint_as_float((u32)tmx_c[uu[i]] << 16), s_pw[qb + (u32)i]); }
                 float sfx = 0.f;
                 u32 ness = 0;
 #pragma unroll
@@ -1027,6 +1136,10 @@ __global__ void __launch_bounds__(SA_ST_NT, 4) sa_k_bm25_stage(const StageParams
             }
             SA_SPT(4);
             // ---- the stage's loads land
+#ifdef SA_PROBE
+            __builtin_amdgcn_s_waitcnt(0x0F70);                  // (vmcnt(0): the probe build charges the wait for the loads to a section of its own)
+            SA_SPT(25);
+#endif
 #pragma unroll
             for (int i = 0; i < 2; i++) if (bro[i] != 0xFFFFFFF0u) ((sa_v4u*)s_bits)[bdst_of((u32)i * NT + tid)] = bv[i];
 #pragma unroll
@@ -1072,16 +1185,16 @@ __global__ void __launch_bounds__(SA_ST_NT, 4) sa_k_bm25_stage(const StageParams
                     u32 u_src = 0; float w_src = 0.f;
 #pragma unroll
                     for (int c = 0; c < TMAX; c++) if ((u32)c == i) { u_src = up[c]; w_src = wp[c]; }
-                    const u64 vsrc = s_post[(s_off[u_src] >> 16) + j];
+                    const u64 vsrc = s_post[(off_c[u_src] >> 16) + j];
                     const u32 od = ((u32)(vsrc >> 32) >> 2) - (u32)tile_d0;
                     // what the other terms can add: all of them in this tile, less the probed terms the doc does not hold (presence bitmaps)
-                    float rem = s_psfx[qb] - __fmul_rn(__uint_as_float(s_tmax[u_src]), w_src);
+                    float rem = s_psfx[qb] - __fmul_rn(__uint_as_float((u32)tmx_c[u_src] << 16), w_src);
                     u32 tmp[TMAX], bwp[TMAX];
 #pragma unroll
                     for (int c = 0; c < TMAX; c++) {
                         const bool pr = up[c] != SA_ST_NONE && up[c] >= NS && up[c] - NS < sp.NPB;
                         const u32 slot = pr ? up[c] - NS : 0u;
-                        tmp[c] = s_tmax[pr ? up[c] : 0u];
+                        tmp[c] = (u32)tmx_c[pr ? up[c] : 0u] << 16;
                         bwp[c] = pr ? s_bits[slot * (u32)SA_ST_BW + (od >> 5)] : 0xFFFFFFFFu;
                     }
 #pragma unroll
@@ -1128,7 +1241,7 @@ __global__ void __launch_bounds__(SA_ST_NT, 4) sa_k_bm25_stage(const StageParams
                     const float thr_f = __uint_as_float(s_thr[q]);
                     u32 pk[TMAX], tmx[TMAX];
 #pragma unroll
-                    for (int i = 0; i < TMAX; i++) { const u32 uu = up[i] != SA_ST_NONE ? up[i] : 0u; pk[i] = s_off[uu]; tmx[i] = s_tmax[uu]; }
+                    for (int i = 0; i < TMAX; i++) { const u32 uu = up[i] != SA_ST_NONE ? up[i] : 0u; pk[i] = off_c[uu]; tmx[i] = (u32)tmx_c[uu] << 16; }
                     u32 pk_src = 0; float w_src = 0.f, ub_src = 0.f;
 #pragma unroll
                     for (int i = 0; i < TMAX; i++) if ((u32)i == i_src) { pk_src = pk[i]; w_src = wp[i]; ub_src = __fmul_rn(__uint_as_float(tmx[i]), wp[i]); }
@@ -1226,6 +1339,7 @@ __global__ void __launch_bounds__(SA_ST_NT, 4) sa_k_bm25_stage(const StageParams
             ptiles++;
 #endif
         }
+        if constexpr (PIPE) hcur ^= 1u;
     }
     flush_finalists();
 #ifdef SA_PROBE
@@ -1237,6 +1351,8 @@ __global__ void __launch_bounds__(SA_ST_NT, 4) sa_k_bm25_stage(const StageParams
         atomicAdd(&g_sa_stage_probe[26], 1ull);
         atomicAdd(&g_sa_stage_probe[27], (unsigned long long)pfin);
         atomicAdd(&g_sa_stage_probe[28], (unsigned long long)pflush);
+        atomicAdd(&g_sa_stage_probe[29], pacc[24]);             // (the sections added behind the counts: prepare_next_tile, stage_loads_wait)
+        atomicAdd(&g_sa_stage_probe[30], pacc[25]);
     }
 #endif
 }
@@ -1287,18 +1403,29 @@ int sa_launch_stage(sa_batch* bt, const Bm25Params& p, hipStream_t st) {
         u32 cw = (u32)std::max<long long>(1, sa_opt(bt->opts.stage_cw, 32));
         while (cw > 1u && wpx % cw != 0u) cw >>= 1;              // (the largest power-of-two share of an XCD's workgroups at most the wish)
         sp.cw = (x.all_rowed && cw > 1u && sp.tpw >= 2u) ? cw : 1u;
-        if (sa_opt(bt->opts.trace, 0)) fprintf(stderr, "sa_launch_stage: rows %u..%u: %u workgroups, %u tiles of %u docs, %u per workgroup, co-walking groups of %u\n", x.q0, x.q0 + x.nq, grid, sp.n_st, sp.docs, sp.tpw, sp.cw);
         const bool one = x.NS <= (u32)SA_ST_NT;
+        // the tile loop pipelined by one tile (option stage_pipe: 1 wherever eligible, 0 never; unset: the rule below).  Eligible: one staged
+        // term per thread -- the two-per-thread instances have no LDS left for the second half of s_off -- and every staged term with a
+        // directory row (a walked term's cursor is a dependent chain per tile).  The layout work the pipeline takes off the chain grows with
+        // the staged terms; with few of them there is nothing to hide and the second copy of the layout code only costs.  Measured
+        // (profiles/stage_kernel_pipelined_prepare_ab_r07.jsonl, 10 M docs, k = 10, pipelined against not, by staged terms): 8 terms
+        // +1.5 .. +10 %, 16 +7.5 %, 32 +0.9 %, 64 +0.9 %, 128 +0.9 %, 251 -0.8 %, 476 -2.6 % (k = 1 / 32: -3.1 / -2.6 %; 1.25 M docs -0.6 %)
+        // -- from 256 staged terms on
+        const long long pipe_opt = sa_opt(bt->opts.stage_pipe, -1);
+        const bool pipe = one && x.all_rowed && (pipe_opt == 1 || (pipe_opt != 0 && x.NS >= 256u));
+        if (sa_opt(bt->opts.trace, 0)) fprintf(stderr, "sa_launch_stage: rows %u..%u: %u workgroups, %u tiles of %u docs, %u per workgroup, co-walking groups of %u, tile loop %s\n", x.q0, x.q0 + x.nq, grid, sp.n_st, sp.docs, sp.tpw, sp.cw, pipe ? "pipelined" : "not pipelined");
         sp.filt = (const u32*)p.filt;
         if (sp.filt && (x.docs > 32u * (u32)SA_ST_BW || x.docs % 64u != 0u)) { sa_set_error("staged route: a filtered tile must be a multiple of 64 docs, at most 1024"); return SA_ERR_STATE; }
         const bool filt = sp.filt != nullptr;
+#define SA_ST_LAUNCH(TM, K, F, PP) hipLaunchKernelGGL((sa_k_bm25_stage<TM, K, F, PP>), dim3(grid), dim3(SA_ST_NT), 0, st, sp)
+#define SA_ST_LAUNCH_F(TM, K, PP) do { if (filt) SA_ST_LAUNCH(TM, K, true, PP); else SA_ST_LAUNCH(TM, K, false, PP); } while (0)
         if (x.tmax == 4) {
-            if (one) { if (filt) hipLaunchKernelGGL((sa_k_bm25_stage<4, 1, true>), dim3(grid), dim3(SA_ST_NT), 0, st, sp); else hipLaunchKernelGGL((sa_k_bm25_stage<4, 1, false>), dim3(grid), dim3(SA_ST_NT), 0, st, sp); }
-            else { if (filt) hipLaunchKernelGGL((sa_k_bm25_stage<4, 2, true>), dim3(grid), dim3(SA_ST_NT), 0, st, sp); else hipLaunchKernelGGL((sa_k_bm25_stage<4, 2, false>), dim3(grid), dim3(SA_ST_NT), 0, st, sp); }
+            if (pipe) SA_ST_LAUNCH_F(4, 1, true); else if (one) SA_ST_LAUNCH_F(4, 1, false); else SA_ST_LAUNCH_F(4, 2, false);
         } else {
-            if (one) { if (filt) hipLaunchKernelGGL((sa_k_bm25_stage<8, 1, true>), dim3(grid), dim3(SA_ST_NT), 0, st, sp); else hipLaunchKernelGGL((sa_k_bm25_stage<8, 1, false>), dim3(grid), dim3(SA_ST_NT), 0, st, sp); }
-            else { if (filt) hipLaunchKernelGGL((sa_k_bm25_stage<8, 2, true>), dim3(grid), dim3(SA_ST_NT), 0, st, sp); else hipLaunchKernelGGL((sa_k_bm25_stage<8, 2, false>), dim3(grid), dim3(SA_ST_NT), 0, st, sp); }
+            if (pipe) SA_ST_LAUNCH_F(8, 1, true); else if (one) SA_ST_LAUNCH_F(8, 1, false); else SA_ST_LAUNCH_F(8, 2, false);
         }
+#undef SA_ST_LAUNCH_F
+#undef SA_ST_LAUNCH
     }
     return SA_OK;
 }

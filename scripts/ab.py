@@ -122,9 +122,10 @@ def main():
                                  "a_search", "a_check", "a_compact", "a_barrier", "b_round_head", "b_lookups", "b_compact", "b_barrier", "before_flush", "flush_atomics_append", "flush_refresh_and_barriers", "flush_probes_and_score"]
                         # (round 7, behind the counts: the next tile's layout built in the load shadow; the explicit wait for the stage loads --
                         #  with it, "stage_loads_landed_and_written" is the LDS writes alone.  Zero in a round-6 probe build.)
+                        # (round 8, slot 31: stage A's survivors per pass -- stage B's load; zero in an older probe build)
                         cycles = {nm: round(v[i] / passes, 1) for i, nm in enumerate(names)}
                         cycles.update({"prepare_next_tile": round(v[29] / passes, 1), "stage_loads_wait": round(v[30] / passes, 1)})
-                        probe = {"tile_passes": v[24], "workgroups": v[26], "candidates_per_pass": round(v[25] / passes, 1), "finalists_per_pass": round(v[27] / passes, 1), "flushes_per_pass": round(v[28] / passes, 2),
+                        probe = {"tile_passes": v[24], "workgroups": v[26], "candidates_per_pass": round(v[25] / passes, 1), "survivors_per_pass": round(v[31] / passes, 1), "finalists_per_pass": round(v[27] / passes, 1), "flushes_per_pass": round(v[28] / passes, 2),
                                  "cycles_per_pass": cycles,
                                  "cycles_per_pass_total": round((sum(v[:24]) + v[29] + v[30]) / passes, 1),
                                  "note": "s_memtime of wave 0 at the phase boundaries (shader cycles); one launch"}

@@ -648,6 +648,7 @@ __global__ void __launch_bounds__(SA_ST_NT, 4) sa_k_bm25_stage(const StageParams
     static_assert(SA_ST_UMAX <= CAP, "a single document's postings must fit the stage");
     static_assert(CAP <= 8192 && SA_ST_UMAX <= 1024, "13-bit stage cells in a chunk descriptor");
     static_assert(SA_ST_BMAX <= 256 && TMAX <= 8, "8-bit query, 3-bit position in a work-list record");
+    static_assert(SA_ST_NONE - SA_ST_UMAX >= (u32)SaStNpb<TMAX>::v, "u - NS < NPB is false for SA_ST_NONE (and wraps for a staged term): one compare tells a probed term with a staged bitmap");
     __shared__ alignas(16) u64 s_post[CAP];                      // the stage: every staged term's slice of this tile, doc-sorted
     __shared__ u32 s_off[(PIPE ? 2 : 1) * SA_ST_UMAX];          // per distinct term: first cell << 16 | postings; a probed term: probe row << 16 | SA_ST_PROBE (PIPE: two halves, tiles alternate)
     __shared__ unsigned short s_tmax[(PIPE ? 2 : 1) * SA_ST_UMAX];  // bound of its factors in this tile: the UPPER 16 bits of the fp32 pattern, rounded up (what a cm word holds)
@@ -678,7 +679,7 @@ __global__ void __launch_bounds__(SA_ST_NT, 4) sa_k_bm25_stage(const StageParams
     u64 pacc[26];
     for (int i = 0; i < 26; i++) pacc[i] = 0;
     u64 plast = __builtin_amdgcn_s_memtime();
-    u32 ptiles = 0, pcand = 0, pfin = 0, pflush = 0;
+    u32 ptiles = 0, pcand = 0, pfin = 0, pflush = 0, psurv = 0;
 #endif
     // XCD-aware tile ranges: block b runs on XCD b % 8; an XCD walks a contiguous range of tiles and its workgroups
     // contiguous sub-ranges -- a term's slices of neighbouring tiles are neighbours in memory, so the cache line a slice
@@ -1182,9 +1183,7 @@ __global__ void __launch_bounds__(SA_ST_NT, 4) sa_k_bm25_stage(const StageParams
                     u32 up[TMAX]; float wp[TMAX];
 #pragma unroll
                     for (int c = 0; c < TMAX; c++) { up[c] = s_pu[qb + (u32)c]; wp[c] = s_pw[qb + (u32)c]; }
-                    u32 u_src = 0; float w_src = 0.f;
-#pragma unroll
-                    for (int c = 0; c < TMAX; c++) if ((u32)c == i) { u_src = up[c]; w_src = wp[c]; }
+                    const u32 u_src = s_pu[qb + i]; const float w_src = s_pw[qb + i];      // (read again, not selected out of up[] / wp[]: two reads for a dozen selects)
                     const u64 vsrc = s_post[(off_c[u_src] >> 16) + j];
                     const u32 od = ((u32)(vsrc >> 32) >> 2) - (u32)tile_d0;
                     // what the other terms can add: all of them in this tile, less the probed terms the doc does not hold (presence bitmaps)
@@ -1192,8 +1191,10 @@ __global__ void __launch_bounds__(SA_ST_NT, 4) sa_k_bm25_stage(const StageParams
                     u32 tmp[TMAX], bwp[TMAX];
 #pragma unroll
                     for (int c = 0; c < TMAX; c++) {
-                        const bool pr = up[c] != SA_ST_NONE && up[c] >= NS && up[c] - NS < sp.NPB;
-                        const u32 slot = pr ? up[c] - NS : 0u;
+                        // probed with a staged bitmap: NS <= u < NS + NPB, one unsigned compare (SA_ST_NONE - NS is never below NPB: see the static_assert)
+                        const u32 slot_c = up[c] - NS;
+                        const bool pr = slot_c < sp.NPB;
+                        const u32 slot = pr ? slot_c : 0u;
                         tmp[c] = (u32)tmx_c[pr ? up[c] : 0u] << 16;
                         bwp[c] = pr ? s_bits[slot * (u32)SA_ST_BW + (od >> 5)] : 0xFFFFFFFFu;
                     }
@@ -1215,6 +1216,9 @@ __global__ void __launch_bounds__(SA_ST_NT, 4) sa_k_bm25_stage(const StageParams
                 __syncthreads();
                 SA_SPT(15);
                 const u32 nb = s_nb;
+#ifdef SA_PROBE
+                psurv += nb;
+#endif
                 // ---- stage B, the survivors, one per lane: the document is looked up in the query's other STAGED terms, in
                 //      descending-bound order, as long as what is known plus what the remaining terms can add reaches the bound;
                 //      the documents that get through are the FINALISTS (s_c: query, doc, the contributions found).  They wait
@@ -1353,6 +1357,7 @@ __global__ void __launch_bounds__(SA_ST_NT, 4) sa_k_bm25_stage(const StageParams
         atomicAdd(&g_sa_stage_probe[28], (unsigned long long)pflush);
         atomicAdd(&g_sa_stage_probe[29], pacc[24]);             // (the sections added behind the counts: prepare_next_tile, stage_loads_wait)
         atomicAdd(&g_sa_stage_probe[30], pacc[25]);
+        atomicAdd(&g_sa_stage_probe[31], (unsigned long long)psurv);      // (stage A's survivors: stage B's load)
     }
 #endif
 }

@@ -127,13 +127,21 @@ __device__ __forceinline__ bool sa_span_keep(const u32* m, int T, bool wrap) {
 }
 
 // header 0 in L?  (the `L - 1` widening is lost then, see the top of the file).  Also clears the query's device
-// counters (cnt layout: sa_span_counts_device), so no separate fill is enqueued for them.
+// counters (cnt layout: SA_SPAN_CNT_* below), so no separate fill is enqueued for them.
 #define SA_SPAN_SORT_MIN 131072         // words of term 0 (an upper bound of the document groups) from which the groups are put in work order
 #define SA_SPAN_INLINE_SCAN 4096       // up to this many chunks (8 M words) the emit pass scans the chunk counts itself
 #define SA_SPAN_NBINS 32                 // work bins of the fast pass (positions of a document group, saturated)
+// The counter block `cnt` of a phrase on the general route, in u32 words (SA_SPAN_MAX_TERMS == 32):
+//   [  0 + t] NCAND   candidate words of term t            [ 32 + t] NHEADS  document groups of term t
+//   [ 64]     WRAP    header 0 in L (sa_k_span_wrap_flag)  [ 96 + t] FILTER  lengths the position filter leaves (the mirror: its hit count)
+//   [128]     OVER    groups the fast pass abandoned       [160 .. 192) BINS bin sizes, [192 .. 224) bin cursors
+#define SA_SPAN_CNT_NCAND 0
+#define SA_SPAN_CNT_NHEADS (1 * SA_SPAN_MAX_TERMS)
+#define SA_SPAN_CNT_WRAP (2 * SA_SPAN_MAX_TERMS)
+#define SA_SPAN_CNT_FILTER (3 * SA_SPAN_MAX_TERMS)
+#define SA_SPAN_CNT_OVER (4 * SA_SPAN_MAX_TERMS)
 #define SA_SPAN_CNT_BINS (5 * SA_SPAN_MAX_TERMS)                     // [.. + NBINS) bin sizes, [.. + 2 NBINS) bin cursors
 #define SA_SPAN_CNT_WORDS (5 * SA_SPAN_MAX_TERMS + 2 * SA_SPAN_NBINS)
-#define SA_SPAN_CNT_WRAP (2 * SA_SPAN_MAX_TERMS)
 __global__ void __launch_bounds__(256) sa_k_span_wrap_flag(const SpanTerms st, u32* __restrict__ cnt) {
     if (blockIdx.x != 0) return;
     if (cnt && threadIdx.x < SA_SPAN_CNT_WORDS && threadIdx.x != SA_SPAN_CNT_WRAP) cnt[threadIdx.x] = 0u;
@@ -307,7 +315,7 @@ sa_k_span_compact_count(const SpanTerms st, const SpanChunkTab ck, const unsigne
     sa_span_compact_count_body(st, ck, flags, chunk_counts, n_chunks, blockIdx.x, gridDim.x);
 }
 
-// block b: exclusive scan of the chunk counts of term b % T, output b / T; totals -> cnt[t] / cnt[16 + t]
+// block b: exclusive scan of the chunk counts of term b % T, output b / T; totals -> cnt[SA_SPAN_CNT_NCAND + t] / cnt[SA_SPAN_CNT_NHEADS + t]
 __global__ void __launch_bounds__(1024)
 sa_k_span_compact_scan(const SpanChunkTab ck, int T, u32* __restrict__ chunk_counts, u32 n_chunks, u32* __restrict__ cnt) {
     __shared__ u32 red[16];
@@ -1960,44 +1968,6 @@ __global__ void __launch_bounds__(SA_SPAN_FT) sa_k_span_doc_fused_multi(const Sp
     sa_span_doc_fused_body<TT, NTAB>(p, wb);
 }
 
-static bool sa_opt_span_doc(const sa_index* ix) { return sa_opt(ix->opts.span_doc, 1) != 0; }
-
-template <int TT>
-static void sa_span_doc_launch(const SpanDocParams& p, dim3 fg, hipStream_t st) {
-    hipLaunchKernelGGL((sa_k_span_doc_fused<TT>), fg, dim3(SA_SPAN_FT), 0, st, p);
-}
-
-static int sa_span_counts_doc_route(sa_index* ix, const SpanTerms& terms_dev, int T, int slop, float** d_out) {
-    hipStream_t st = ix->stream;
-    const u64 N = ix->n_docs;
-    void* scratch;
-    SA_TRY(sa_index_scratch(ix, (N + 64) * 4, &scratch));
-    SpanDocParams p;
-    memset(&p, 0, sizeof(p));
-    p.st = terms_dev;
-    p.st.off[0] = 0;
-    for (int t = 0; t < T; t++) p.st.off[t + 1] = p.st.off[t] + p.st.len[t];
-    p.slop = (u32)slop;
-    p.counts = (float*)scratch;
-    *d_out = p.counts;
-    // the documents to look at: those of the rarest term -- unless its list is about as long as the collection (then
-    // every document, in doc order: no search for the openers, nothing to clear beforehand)
-    int rarest = 0;
-    for (int t = 1; t < T; t++) if (terms_dev.len[t] < terms_dev.len[rarest]) rarest = t;
-    p.anchor = 2 * (u64)terms_dev.len[rarest] >= N ? -1 : rarest;
-    if (p.anchor >= 0) SA_HIP(hipMemsetAsync(p.counts, 0, N * sizeof(float), st));
-    if (sa_opt(ix->opts.trace, 0)) fprintf(stderr, "slop doc route: %s\n", p.anchor >= 0 ? "over the rarest term's documents" : "over all documents");
-    const u64 slots = p.anchor >= 0 ? (u64)terms_dev.len[rarest] : N;
-    const dim3 fg((u32)((slots + SA_SPAN_FD - 1) / SA_SPAN_FD));
-    switch (T) {
-    case 2: sa_span_doc_launch<2>(p, fg, st); break;
-    case 3: sa_span_doc_launch<3>(p, fg, st); break;
-    default: sa_span_doc_launch<4>(p, fg, st); break;
-    }
-    SA_HIP(hipGetLastError());
-    return SA_OK;
-}
-
 // ---- B slop phrases in SHARED launches (phrase batches, BASELINE config 5) ------------------------------------------
 // A sampled slop phrase is five short launches, and a batch of them is bound by the host's launch rate (round 2: 25 K
 // phrases/s over two streams).  Here every stage is ONE launch for all phrases of a class (2, 3, 4 terms, more):
@@ -2079,54 +2049,184 @@ __global__ void __launch_bounds__(64) sa_k_span_machine(const SpanMachineParams 
     }
 }
 
+// ---- the host plan of a slop > 0 phrase: which kernels run, on which scratch, in which grids -------------------------
+// One phrase (sa_span_counts_device) and the phrases of a batch in shared launches (sa_span_counts_batch) go by the same
+// rules.  Each rule is ONE function here; what the two entry points do differently is policy, written at their call sites.
+// The instantiations of the templated kernels, one table per family: `launch` is handed the template arguments as
+// SpanInt values, so the single-phrase and the batch kernel of a family (another name, another argument pack) share it.
+template <int V> using SpanInt = std::integral_constant<int, V>;
+// flags kernels: the number of terms when it is 2, 3 or 4, else 0 (any number)
+template <class F> static void sa_span_flags_by_terms(int T, F launch) {
+    if (T == 2) launch(SpanInt<2>()); else if (T == 3) launch(SpanInt<3>()); else if (T == 4) launch(SpanInt<4>()); else launch(SpanInt<0>());
+}
+// fast pass <CE, PMAX, TT> -- table size: two-term documents rarely need more than 12 spans; with three terms and more
+// 15 % of them do (3 % more than 16, < 1 % more than 20), and the heavy pass (a wave per document) costs more than the
+// lower residency of a larger table
+template <class F> static void sa_span_flat_by_terms(int T, F launch) {
+    if (T == 2) launch(SpanInt<SA_SPAN_LDS>(), SpanInt<SA_SPAN_PMAX>(), SpanInt<2>());
+    else if (T == 3) launch(SpanInt<20>(), SpanInt<20>(), SpanInt<3>());
+    else launch(SpanInt<20>(), SpanInt<20>(), SpanInt<0>());
+}
+// doc-parallel kernels: 2, 3 or 4 terms (sa_span_doc_route_ok admits no other)
+template <class F> static void sa_span_doc_by_terms(int T, F launch) {
+    if (T == 2) launch(SpanInt<2>()); else if (T == 3) launch(SpanInt<3>()); else launch(SpanInt<4>());
+}
+
+static bool sa_opt_span_doc(const sa_index* ix) { return sa_opt(ix->opts.span_doc, 1) != 0; }
+
+// The lists of terms[0 .. T): words, len and -- use_dd: whole, unfiltered lists only -- the doc directory row of a frequent term
+// without a top-block word.  False: a term the index does not have (its slot stays empty).  *total_len: the words of all lists.
+static bool sa_span_resolve_terms(const sa_index* ix, const u32* terms, int T, bool use_dd, SpanTerms* st, size_t* total_len) {
+    memset(st, 0, sizeof(*st));
+    st->T = T; st->n_docs = ix->n_docs;
+    bool known = true;
+    *total_len = 0;
+    for (int t = 0; t < T; t++) {
+        if (terms[t] >= ix->n_terms) { known = false; continue; }
+        const u64 off = ix->h_term_off[terms[t]];
+        st->words[t] = ix->d_words + off;
+        st->len[t] = (u32)(ix->h_term_off[terms[t] + 1] - off);
+        if (use_dd) {
+            const u32 sl = ix->h_dd_slot[terms[t]];
+            if (sl != SA_DD_NONE && sl < ix->h_dd_top.size() && ix->h_dd_top[sl] == 0) st->dd[t] = ix->d_docdir + (size_t)sl * ix->n_docs;
+        }
+        *total_len += st->len[t];
+    }
+    return known;
+}
+
+static void sa_span_prefix(SpanTerms* st) {              // off: position of each term in the flag array
+    st->off[0] = 0;
+    for (int t = 0; t < st->T; t++) st->off[t + 1] = st->off[t] + st->len[t];
+}
+
+// header 0 in L?  (the `L - 1` widening is lost then, see the top of the file.)  Whole lists: host arithmetic on the
+// index's per-term edge flags (sa_k_term_edges; the caller checks that h_term_edge covers the terms).  Lists cut by a
+// position filter: sa_k_span_wrap_flag looks at the filtered words.
+static bool sa_span_header0_in_L(const sa_index* ix, const u32* terms, int T) {
+    const unsigned char e0 = ix->h_term_edge[terms[0]];
+    bool L = true;
+    for (int i = 1; i < T; i++) {
+        const unsigned char ei = ix->h_term_edge[terms[i]];
+        const bool a0 = e0 & 1, a0m = e0 & 2, bi = ei & 1, bim = ei & 2;
+        L &= (a0 && bi) || (bi && a0m) || (a0 && bim);
+    }
+    return L;
+}
+
+// The doc-parallel route (sa_k_span_doc_fused: gather, work order and span machines per block of documents, nothing but
+// the lists read), whatever the lists' lengths: 2..4 known terms, none empty, no word of these lists in a document's last
+// 18-position block -- no such word in the index at all (the usual case), or every term with a directory row that says
+// so --, header 0 not in L.
+// (two terms: the `L - 1` widening adds nothing -- a word at h with L(h + 1) has R(h), whichever clause of
+//  Lset(h + 1) holds and whichever term the word is of -- so its loss changes nothing either)
+// (it wins on every phrase measured, short lists included -- zipf-1M, slop 2, [0 1] 0.078 vs 0.130 ms, [5 6] 0.030 vs
+//  0.059, [20 30] 0.022 vs 0.034, [5 8 9] 0.040 vs 0.070: one launch against seven)
+// The options (span_doc, span_doc_multi) and the position filter stay with the callers.  why: what the single route's
+// trace line shows (shape: the phrase got as far as the look at its lists).
+struct SpanDocWhy { bool shape, all_dd, in_L; };
+static bool sa_span_doc_route_ok(const sa_index* ix, const SpanTerms& st, const u32* terms, int T, int slop, SpanDocWhy* why = nullptr) {
+    const u64 N = st.n_docs;
+    SpanDocWhy w = {false, true, true};
+    bool nonempty = true;
+    w.shape = T >= 2 && T <= 4 && T + slop <= 15 && N > 0 && N < 0xFFFFFFF0ull && ix->h_term_edge.size() >= (size_t)ix->n_terms;
+    if (w.shape) {
+        for (int t = 0; t < T; t++) { w.all_dd = w.all_dd && st.dd[t] != nullptr; nonempty = nonempty && st.len[t] > 0; }
+        w.in_L = sa_span_header0_in_L(ix, terms, T);
+    }
+    if (why) *why = w;
+    return w.shape && nonempty && (w.all_dd || !ix->any_top_block) && (T == 2 || !w.in_L);
+}
+
+// The doc-parallel route's parameters, all but where the result goes.  The documents to look at: those of the rarest
+// term -- unless its list is about as long as the collection (then every document, in doc order: no search for the
+// openers, nothing to clear beforehand); n_blocks: the phrase's blocks (a launch of its own: the grid).
+static void sa_span_doc_params(const SpanTerms& st, int T, int slop, u64 N, SpanDocParams* p) {
+    memset(p, 0, sizeof(*p));
+    p->st = st;
+    sa_span_prefix(&p->st);
+    p->slop = (u32)slop;
+    int rarest = 0;
+    for (int t = 1; t < T; t++) if (st.len[t] < st.len[rarest]) rarest = t;
+    p->anchor = 2 * (u64)st.len[rarest] >= N ? -1 : rarest;
+    const u64 slots = p->anchor >= 0 ? (u64)st.len[rarest] : N;
+    p->n_blocks = (u32)((slots + SA_SPAN_FD - 1) / SA_SPAN_FD);
+}
+
+// Scratch of the general route.  A bump allocator: with a null base it only counts (the batch sizes its pool before it
+// has one), with the real base it hands out the pointers -- the same carving code serves both.
+struct SpanBump {
+    char* base; size_t used;
+    template <class X> X* take(size_t n) { X* p = base ? (X*)(base + used) : nullptr; used += (n * sizeof(X) + 255) & ~(size_t)255; return p; }
+};
+
+// the buffers of a phrase that do not depend on what a position filter leaves: the counter block (layout: SA_SPAN_CNT_*),
+// the chunk counters, the keep-flags of all words, the groups the fast pass abandons (len0: an upper bound of the groups)
+static void sa_span_carve(SpanBump& b, size_t chunk_words, size_t flag_bytes, u32 len0, u32** cnt, u32** chunks, unsigned char** flags, u32** over_list) {
+    *cnt = b.take<u32>(SA_SPAN_CNT_WORDS);
+    *chunks = b.take<u32>(chunk_words);
+    *flags = b.take<unsigned char>(flag_bytes);
+    *over_list = b.take<u32>((size_t)len0 + 64);
+}
+// ... and per term (the lists as the kernels see them) the candidate words, the document groups' heads and positions;
+// the compaction writes them, the machines read them and their lengths in cnt
+static void sa_span_carve_terms(SpanBump& b, const SpanTerms& st, u32* cnt, SpanCompactOut* co, SpanMachineParams* mp) {
+    for (int t = 0; t < st.T; t++) {
+        u64* cand = b.take<u64>((size_t)st.len[t] + 1);
+        u32* heads = b.take<u32>((size_t)st.len[t] + 1);
+        co->gpos[t] = b.take<unsigned char>((size_t)st.len[t] + 1);
+        if (!cnt) continue;                                          // (counting)
+        co->cand[t] = cand; co->heads[t] = heads;
+        mp->cand[t] = cand; mp->n_cand[t] = cnt + SA_SPAN_CNT_NCAND + t;
+        mp->heads[t] = heads; mp->n_heads[t] = cnt + SA_SPAN_CNT_NHEADS + t;
+    }
+}
+// the fast pass lists the groups it abandons, the heavy pass takes them
+static void sa_span_wire_over(SpanMachineParams* mp, u32* cnt, u32* over_list) {
+    if (!cnt) return;                                                // (counting)
+    mp->over_list = over_list; mp->in_list = over_list; mp->over_cnt = cnt + SA_SPAN_CNT_OVER; mp->in_cnt = cnt + SA_SPAN_CNT_OVER;
+}
+
+// chunks of every term for the one compaction; returns their number
+static u32 sa_span_chunk_tab(const SpanTerms& st, SpanChunkTab* ck) {
+    ck->coff[0] = 0;
+    for (int t = 0; t < SA_SPAN_MAX_TERMS; t++) ck->coff[t + 1] = ck->coff[t] + (t < st.T ? sa_compact_chunks(st.len[t]) : 0u);
+    return ck->coff[st.T];
+}
+
+static int sa_span_counts_doc_route(sa_index* ix, const SpanTerms& terms_dev, int T, int slop, float** d_out) {
+    hipStream_t st = ix->stream;
+    const u64 N = ix->n_docs;
+    void* scratch;
+    SA_TRY(sa_index_scratch(ix, (N + 64) * 4, &scratch));
+    SpanDocParams p;
+    sa_span_doc_params(terms_dev, T, slop, N, &p);
+    p.counts = (float*)scratch;
+    *d_out = p.counts;
+    if (p.anchor >= 0) SA_HIP(hipMemsetAsync(p.counts, 0, N * sizeof(float), st));
+    if (sa_opt(ix->opts.trace, 0)) fprintf(stderr, "slop doc route: %s\n", p.anchor >= 0 ? "over the rarest term's documents" : "over all documents");
+    sa_span_doc_by_terms(T, [&](auto tt) { hipLaunchKernelGGL((sa_k_span_doc_fused<decltype(tt)::value>), dim3(p.n_blocks), dim3(SA_SPAN_FT), 0, st, p); });
+    SA_HIP(hipGetLastError());
+    return SA_OK;
+}
+
 // dense slop > 0 phrase counts of terms[0..T) -> *d_out (float[n_docs], inside the index scratch)
 int sa_span_counts_device(sa_index* ix, const u32* terms, int T, int slop, const PosnFilter& filt, float** d_out) {
     if (T > SA_SPAN_MAX_TERMS) { sa_set_error("slop phrases support at most %d terms", SA_SPAN_MAX_TERMS); return SA_ERR_UNSUPPORTED; }
     hipStream_t st = ix->stream;
     const u64 N = ix->n_docs;
+    // (directory rows: whole lists only, so not under a position filter)
+    const bool use_dd = !filt.active && ix->n_dd_terms > 0 && sa_opt(ix->opts.span_docdir, 1) != 0;
     SpanTerms terms_dev;
-    memset(&terms_dev, 0, sizeof(terms_dev));
-    terms_dev.T = T;
-    terms_dev.n_docs = ix->n_docs;
-    bool known = true;
     size_t total_len = 0, max_len = 0;
-    for (int t = 0; t < T; t++) {
-        if (terms[t] >= ix->n_terms) { known = false; continue; }
-        const u64 off = ix->h_term_off[terms[t]];
-        terms_dev.words[t] = ix->d_words + off;
-        terms_dev.len[t] = (u32)(ix->h_term_off[terms[t] + 1] - off);
-        // probes through the doc directory (whole, unfiltered lists of frequent terms without a top-block word)
-        if (!filt.active && ix->n_dd_terms > 0 && sa_opt(ix->opts.span_docdir, 1) != 0) {
-            const u32 sl = ix->h_dd_slot[terms[t]];
-            if (sl != SA_DD_NONE && sl < ix->h_dd_top.size() && ix->h_dd_top[sl] == 0)
-                terms_dev.dd[t] = ix->d_docdir + (size_t)sl * ix->n_docs;
-        }
-        total_len += terms_dev.len[t];
-        if (terms_dev.len[t] > max_len) max_len = terms_dev.len[t];
-    }
+    const bool known = sa_span_resolve_terms(ix, terms, T, use_dd, &terms_dev, &total_len);
+    for (int t = 0; t < T; t++) max_len = std::max<size_t>(max_len, terms_dev.len[t]);
     if (total_len > 0xFFFFFFF0ull) { sa_set_error("slop phrase: more than 2^32 words in the phrase's terms"); return SA_ERR_UNSUPPORTED; }
-    // the doc-parallel route: 2..4 known terms, all with a directory row (whole lists, no word in a last block), header
-    // 0 not in L (host arithmetic on the per-term edge flags, as below)
-    if (known && !filt.active && T >= 2 && T <= 4 && T + slop <= 15 && N > 0 && N < 0xFFFFFFF0ull && sa_opt_span_doc(ix) &&
-        ix->h_term_edge.size() >= (size_t)ix->n_terms) {
-        // no word of these lists in a document's last 18-position block: no such word in the index at all (the usual case),
-        // or every term with a directory row that says so
-        bool all_dd = true, nonempty = true;
-        for (int t = 0; t < T; t++) { all_dd = all_dd && terms_dev.dd[t] != nullptr; nonempty = nonempty && terms_dev.len[t] > 0; }
-        const bool local = nonempty && (all_dd || !ix->any_top_block);
-        const unsigned char e0 = ix->h_term_edge[terms[0]];
-        bool L = true;
-        for (int i = 1; i < T; i++) {
-            const unsigned char ei = ix->h_term_edge[terms[i]];
-            const bool a0 = e0 & 1, a0m = e0 & 2, bi = ei & 1, bim = ei & 2;
-            L &= (a0 && bi) || (bi && a0m) || (a0 && bim);
-        }
-        // (two terms: the `L - 1` widening adds nothing -- a word at h with L(h + 1) has R(h), whichever clause of
-        //  Lset(h + 1) holds and whichever term the word is of -- so its loss changes nothing either)
-        // (it wins on every phrase measured, short lists included -- zipf-1M, slop 2, [0 1] 0.078 vs 0.130 ms, [5 6] 0.030 vs
-        //  0.059, [20 30] 0.022 vs 0.034, [5 8 9] 0.040 vs 0.070: one launch against seven)
-        const bool take = local && (T == 2 || !L);
-        if (sa_opt(ix->opts.trace, 0)) fprintf(stderr, "slop route: %s (T %d, directory rows %d, header 0 in L %d)\n", take ? "doc-parallel" : "general", T, (int)all_dd, (int)L);
+    if (known && !filt.active && sa_opt_span_doc(ix)) {
+        SpanDocWhy why;
+        const bool take = sa_span_doc_route_ok(ix, terms_dev, terms, T, slop, &why);
+        if (why.shape && sa_opt(ix->opts.trace, 0))
+            fprintf(stderr, "slop route: %s (T %d, directory rows %d, header 0 in L %d)\n", take ? "doc-parallel" : "general", T, (int)why.all_dd, (int)why.in_L);
         if (take) return sa_span_counts_doc_route(ix, terms_dev, T, slop, d_out);
     }
     // resident state-machine threads: no more than there can be document groups
@@ -2144,18 +2244,16 @@ int sa_span_counts_device(sa_index* ix, const u32* terms, int T, int slop, const
                         ((size_t)terms_dev.len[0] + 64) * 13 + 256 * (size_t)T;
     void* scratch;
     SA_TRY(sa_index_scratch(ix, need, &scratch));
-    char* base = (char*)scratch;
-    size_t used = 0;
-    auto take = [&](size_t bytes) { char* p = base + used; used += (bytes + 255) & ~(size_t)255; return p; };
-    float* running = (float*)take((N + 1) * 4);
-    u32* cnt = (u32*)take(SA_SPAN_CNT_WORDS * 4);          // [t] n_cand, [16 + t] n_heads, [32] wrap flag, [48 + t] filter scratch, [64] abandoned groups
-    u32* chunks = (u32*)take(chunk_words * 4);
-    SpanEnt* ents = (SpanEnt*)take((size_t)G * SA_NSPANS * sizeof(SpanEnt));
-    u64* col = (u64*)take((size_t)G * SA_NSPANS * sizeof(u64));
-    unsigned char* flags = (unsigned char*)take(total_len + 64);
-    u32* over_list = (u32*)take(((size_t)terms_dev.len[0] + 64) * 4);
-    u32* order = (u32*)take(((size_t)terms_dev.len[0] + 64) * 4);
-    unsigned char* bins = (unsigned char*)take((size_t)terms_dev.len[0] + 64);
+    SpanBump b = {(char*)scratch, 0};
+    u32 *cnt, *chunks, *over_list;
+    unsigned char* flags;
+    // what only a phrase on its own has: the dense result (at the start of the scratch), the slab machine's tables, the work order
+    float* running = b.take<float>(N + 1);
+    sa_span_carve(b, chunk_words, total_len + 64, terms_dev.len[0], &cnt, &chunks, &flags, &over_list);
+    SpanEnt* ents = b.take<SpanEnt>((size_t)G * SA_NSPANS);
+    u64* col = b.take<u64>((size_t)G * SA_NSPANS);
+    u32* order = b.take<u32>((size_t)terms_dev.len[0] + 64);
+    unsigned char* bins = b.take<unsigned char>((size_t)terms_dev.len[0] + 64);
     *d_out = running;
     if (!known || N == 0 || total_len == 0) {
         SA_HIP(hipMemsetAsync(running, 0, N * sizeof(float), st));
@@ -2168,20 +2266,26 @@ int sa_span_counts_device(sa_index* ix, const u32* terms, int T, int slop, const
         u32 lens[SA_SPAN_MAX_TERMS];
         for (int t = 0; t < T; t++) {
             ptrs[t] = terms_dev.words[t]; lens[t] = terms_dev.len[t];
-            bufs[t] = (u64*)take(((size_t)lens[t] + 1) * 8);
+            bufs[t] = b.take<u64>((size_t)lens[t] + 1);
         }
-        if (used > need) { sa_set_error("internal: span scratch exhausted"); return SA_ERR_STATE; }
-        SA_TRY(sa_posn_filter_terms(ix, filt, T, ptrs, lens, bufs, cnt + 3 * SA_SPAN_MAX_TERMS, chunks));
+        if (b.used > need) { sa_set_error("internal: span scratch exhausted"); return SA_ERR_STATE; }
+        SA_TRY(sa_posn_filter_terms(ix, filt, T, ptrs, lens, bufs, cnt + SA_SPAN_CNT_FILTER, chunks));
         for (int t = 0; t < T; t++) { terms_dev.words[t] = ptrs[t]; terms_dev.len[t] = lens[t]; }
     }
-    terms_dev.off[0] = 0;
-    for (int t = 0; t < T; t++) terms_dev.off[t + 1] = terms_dev.off[t] + terms_dev.len[t];
+    sa_span_prefix(&terms_dev);
     if (terms_dev.off[T] == 0 || terms_dev.len[0] == 0) {         // (the position filter left nothing; term 0 drives the walk)
         SA_HIP(hipMemsetAsync(running, 0, N * sizeof(float), st));
         return SA_OK;
     }
-    // header 0 in L?  Whole lists: host arithmetic on the index's per-term edge flags (sa_k_term_edges); lists cut
-    // by a position filter: sa_k_span_wrap_flag looks at the filtered words.
+    SpanMachineParams mp;
+    memset(&mp, 0, sizeof(mp));
+    mp.T = T; mp.slop = (u32)slop; mp.ents = ents; mp.col = col; mp.fcounts = running; mp.n_docs = N; mp.n_threads = G;
+    SpanChunkTab ck;
+    SpanCompactOut co;
+    memset(&co, 0, sizeof(co));
+    sa_span_carve_terms(b, terms_dev, cnt, &co, &mp);
+    if (b.used > need) { sa_set_error("internal: span scratch exhausted"); return SA_ERR_STATE; }
+    // header 0 in L: on the host, or -- lists cut by a position filter, an index without edge flags -- by a launch
     const u32* wrap_dev = nullptr;
     int wrap_host = 0;
     u32* cnt_clear = cnt;
@@ -2189,16 +2293,7 @@ int sa_span_counts_device(sa_index* ix, const u32* terms, int T, int slop, const
         hipLaunchKernelGGL(sa_k_span_wrap_flag, dim3(1), dim3(256), 0, st, terms_dev, cnt);
         wrap_dev = cnt + SA_SPAN_CNT_WRAP;
         cnt_clear = nullptr;
-    } else {
-        const unsigned char e0 = ix->h_term_edge[terms[0]];
-        bool L = true;
-        for (int i = 1; i < T; i++) {
-            const unsigned char ei = ix->h_term_edge[terms[i]];
-            const bool a0 = e0 & 1, a0m = e0 & 2, bi = ei & 1, bim = ei & 2;
-            L &= (a0 && bi) || (bi && a0m) || (a0 && bim);
-        }
-        wrap_host = L ? 1 : 0;
-    }
+    } else wrap_host = sa_span_header0_in_L(ix, terms, T) ? 1 : 0;
     {
         const u32 total = terms_dev.off[T];
         // (at least a block per 4096 documents: the launch also clears the dense result -- with one block for two
@@ -2206,33 +2301,10 @@ int sa_span_counts_device(sa_index* ix, const u32* terms, int T, int slop, const
         const u32 by_words = total / 256 + 1 < 16384 ? total / 256 + 1 : 16384;
         const u32 by_docs = (u32)std::min<u64>(N / 4096 + 1, 1024);
         const u32 grid = std::max(by_words, by_docs);
-        switch (T) {
-        case 2: hipLaunchKernelGGL(sa_k_span_flags<2>, dim3(grid), dim3(256), 0, st, terms_dev, wrap_dev, wrap_host, cnt_clear, flags, running); break;
-        case 3: hipLaunchKernelGGL(sa_k_span_flags<3>, dim3(grid), dim3(256), 0, st, terms_dev, wrap_dev, wrap_host, cnt_clear, flags, running); break;
-        case 4: hipLaunchKernelGGL(sa_k_span_flags<4>, dim3(grid), dim3(256), 0, st, terms_dev, wrap_dev, wrap_host, cnt_clear, flags, running); break;
-        default: hipLaunchKernelGGL(sa_k_span_flags<0>, dim3(grid), dim3(256), 0, st, terms_dev, wrap_dev, wrap_host, cnt_clear, flags, running); break;
-        }
+        sa_span_flags_by_terms(T, [&](auto tt) { hipLaunchKernelGGL(sa_k_span_flags<decltype(tt)::value>, dim3(grid), dim3(256), 0, st, terms_dev, wrap_dev, wrap_host, cnt_clear, flags, running); });
     }
-    SpanMachineParams mp;
-    memset(&mp, 0, sizeof(mp));
-    mp.T = T; mp.slop = (u32)slop; mp.ents = ents; mp.col = col; mp.fcounts = running; mp.n_docs = N; mp.n_threads = G;
-    SpanChunkTab ck;
-    SpanCompactOut co;
-    memset(&ck, 0, sizeof(ck));
-    memset(&co, 0, sizeof(co));
-    for (int t = 0; t < T; t++) {
-        u64* cand = (u64*)take(((size_t)terms_dev.len[t] + 1) * 8);
-        u32* heads = (u32*)take(((size_t)terms_dev.len[t] + 1) * 4);
-        if (used > need) { sa_set_error("internal: span scratch exhausted"); return SA_ERR_STATE; }
-        mp.cand[t] = cand; mp.n_cand[t] = cnt + t; mp.heads[t] = heads; mp.n_heads[t] = cnt + SA_SPAN_MAX_TERMS + t;
-        co.cand[t] = cand; co.heads[t] = heads;
-        co.gpos[t] = (unsigned char*)take((size_t)terms_dev.len[t] + 1);
-        if (used > need) { sa_set_error("internal: span scratch exhausted"); return SA_ERR_STATE; }
-        ck.coff[t + 1] = ck.coff[t] + sa_compact_chunks(terms_dev.len[t]);
-    }
-    for (int t = T; t < SA_SPAN_MAX_TERMS; t++) ck.coff[t + 1] = ck.coff[t];
     {
-        const u32 n_chunks = ck.coff[T];                       // (> 0: total_len > 0)
+        const u32 n_chunks = sa_span_chunk_tab(terms_dev, &ck);   // (> 0: total_len > 0)
         const u32 grid = n_chunks < 16384u ? n_chunks : 16384u;
         hipLaunchKernelGGL(sa_k_span_compact_count, dim3(grid), dim3(SA_CT), 0, st, terms_dev, ck, (const unsigned char*)flags, chunks, n_chunks);
         const bool inline_scan = n_chunks <= (u32)SA_SPAN_INLINE_SCAN && n_chunks <= 16384u;       // (one chunk per block)
@@ -2242,7 +2314,7 @@ int sa_span_counts_device(sa_index* ix, const u32* terms, int T, int slop, const
     }
     // fast pass (tables in LDS, one thread per document group), then the groups it abandoned with full tables
     if (sa_opt(ix->opts.span_fast, 1) != 0 && terms_dev.len[0] > 0) {
-        mp.over_list = over_list; mp.over_cnt = cnt + 4 * SA_SPAN_MAX_TERMS;
+        sa_span_wire_over(&mp, cnt, over_list);
         // (work order only when the document groups outnumber the lanes the device keeps resident -- 256 CUs x 13 waves
         //  x 64: below that every wave starts at once, the order changes nothing, and a light phrase saves two launches)
         const int sort_env = (int)sa_opt(ix->opts.span_sort, -1);
@@ -2257,13 +2329,9 @@ int sa_span_counts_device(sa_index* ix, const u32* terms, int T, int slop, const
             mp.order = order;
         }
         const dim3 fg((terms_dev.len[0] + 63u) / 64u);
-        // table size: two-term documents rarely need more than 12 spans; with three terms and more 15 % of them do
-        // (3 % more than 16, < 1 % more than 20), and the heavy pass (a wave per document) costs more than the lower
-        // residency of a larger table
-        if (T == 2) hipLaunchKernelGGL((sa_k_span_machine_flat<SA_SPAN_LDS, SA_SPAN_PMAX, 2>), fg, dim3(64), 0, st, mp);
-        else if (T == 3) hipLaunchKernelGGL((sa_k_span_machine_flat<20, 20, 3>), fg, dim3(64), 0, st, mp);
-        else hipLaunchKernelGGL((sa_k_span_machine_flat<20, 20, 0>), fg, dim3(64), 0, st, mp);
-        mp.in_list = over_list; mp.in_cnt = cnt + 4 * SA_SPAN_MAX_TERMS;
+        sa_span_flat_by_terms(T, [&](auto ce, auto pm, auto tt) {
+            hipLaunchKernelGGL((sa_k_span_machine_flat<decltype(ce)::value, decltype(pm)::value, decltype(tt)::value>), fg, dim3(64), 0, st, mp);
+        });
         // (a wave per abandoned group; 1024 blocks striding over the list were measured slower on the heaviest 2-term
         //  query, 0.155 vs 0.140 ms: it abandons thousands of groups)
         const u32 g2 = std::min<u32>(8192u, terms_dev.len[0]);
@@ -2286,10 +2354,8 @@ int sa_span_counts_batch(sa_index* ix, hipStream_t st, int n, const u32* const* 
     *d_rank_jobs = nullptr; *n_rank_jobs = 0;
     const u64 N = ix->n_docs;
     if (n <= 0 || N == 0) return SA_OK;
-    {
-        if (sa_opt(ix->opts.span_fast, 1) == 0 || sa_opt(ix->opts.span_sort, -1) > 0 || sa_opt(ix->opts.span_multi, 1) == 0) return SA_OK;
-        if (ix->h_term_edge.size() < (size_t)ix->n_terms) return SA_OK;
-    }
+    if (sa_opt(ix->opts.span_fast, 1) == 0 || sa_opt(ix->opts.span_sort, -1) > 0 || sa_opt(ix->opts.span_multi, 1) == 0) return SA_OK;
+    if (ix->h_term_edge.size() < (size_t)ix->n_terms) return SA_OK;          // (header 0 in L is host arithmetic here, never a launch)
     const bool use_dd = ix->n_dd_terms > 0 && sa_opt(ix->opts.span_docdir, 1) != 0;
     std::vector<SpanJob> jobs;
     std::vector<SpanDocParams> djobs[3];               // phrases of 2 / 3 / 4 terms on the doc-parallel route
@@ -2299,85 +2365,41 @@ int sa_span_counts_batch(sa_index* ix, hipStream_t st, int n, const u32* const* 
     const bool fused_rank = rank && rank->cand && sa_opt(ix->opts.span_doc_rank, 1) != 0;
     std::vector<int> job_row, job_class;
     std::vector<size_t> job_off;                       // scratch offset of each job
-    size_t used = 0;
-    auto take = [&](size_t bytes) { const size_t o = used; used += (bytes + 255) & ~(size_t)255; return o; };
+    // scratch of a job: counted when the job is taken (no pool yet: b.base is null), bound once the pool is sized
+    auto job_buffers = [](SpanBump& b, SpanJob& J) {
+        u32* over_list;
+        sa_span_carve(b, (size_t)2 * J.n_chunks + 8, (size_t)J.st.off[J.st.T] + 64, J.st.len[0], &J.cnt, &J.chunks, &J.flags, &over_list);
+        sa_span_carve_terms(b, J.st, J.cnt, &J.co, &J.mp);
+        sa_span_wire_over(&J.mp, J.cnt, over_list);
+    };
+    SpanBump pool = {nullptr, 0};
     for (int i = 0; i < n; i++) {
         const int Ti = T[i];
         if (Ti < 2 || Ti > SA_SPAN_MAX_TERMS || slop[i] <= 0) continue;
+        SpanTerms sti;
+        size_t total_len = 0;
+        // (not handled here: an unknown term, an empty term 0, no words at all -- the single route's zeroed result -- and 2^31 words or more)
+        if (!sa_span_resolve_terms(ix, terms[i], Ti, use_dd, &sti, &total_len)) continue;
+        if (total_len == 0 || sti.len[0] == 0 || total_len > 0x7FFFFFF0ull) continue;
+        // the doc-parallel route where the phrase qualifies: ALL such phrases of the batch share one launch per term count
+        if (doc_route && sa_span_doc_route_ok(ix, sti, terms[i], Ti, slop[i])) {
+            djobs[Ti - 2].emplace_back();
+            sa_span_doc_params(sti, Ti, slop[i], N, &djobs[Ti - 2].back());
+            drow[Ti - 2].push_back(i);
+            continue;
+        }
+        if (sti.len[0] > (u32)SA_SPAN_SORT_MIN) continue;                          // (would be put in work order)
         SpanJob J;
         memset(&J, 0, sizeof(J));
-        J.st.T = Ti; J.st.n_docs = N;
-        bool ok = true;
-        size_t total_len = 0;
-        for (int t = 0; t < Ti && ok; t++) {
-            const u32 term = terms[i][t];
-            if (term >= ix->n_terms) { ok = false; break; }
-            const u64 off = ix->h_term_off[term];
-            J.st.words[t] = ix->d_words + off;
-            J.st.len[t] = (u32)(ix->h_term_off[term + 1] - off);
-            if (use_dd) {
-                const u32 sl = ix->h_dd_slot[term];
-                if (sl != SA_DD_NONE && sl < ix->h_dd_top.size() && ix->h_dd_top[sl] == 0) J.st.dd[t] = ix->d_docdir + (size_t)sl * N;
-            }
-            total_len += J.st.len[t];
-        }
-        if (!ok || total_len == 0 || J.st.len[0] == 0 || total_len > 0x7FFFFFF0ull) continue;
-        // the doc-parallel route (sa_k_span_doc_fused: gather, work order and span machines per block of documents, nothing but
-        // the lists read) where the phrase qualifies -- the conditions of sa_span_counts_device -- whatever the lists' lengths:
-        // ALL such phrases of the batch share one launch per term count
-        if (doc_route && Ti <= 4 && Ti + slop[i] <= 15 && N < 0xFFFFFFF0ull) {
-            bool all_dd = true, nonempty = true;
-            for (int t = 0; t < Ti; t++) { all_dd = all_dd && J.st.dd[t] != nullptr; nonempty = nonempty && J.st.len[t] > 0; }
-            const unsigned char e0 = ix->h_term_edge[terms[i][0]];
-            bool L = true;
-            for (int t = 1; t < Ti; t++) {
-                const unsigned char ei = ix->h_term_edge[terms[i][t]];
-                const bool a0 = e0 & 1, a0m = e0 & 2, bi = ei & 1, bim = ei & 2;
-                L &= (a0 && bi) || (bi && a0m) || (a0 && bim);
-            }
-            if (nonempty && (all_dd || !ix->any_top_block) && (Ti == 2 || !L)) {
-                SpanDocParams P;
-                memset(&P, 0, sizeof(P));
-                P.st = J.st;
-                P.st.off[0] = 0;
-                for (int t = 0; t < Ti; t++) P.st.off[t + 1] = P.st.off[t] + P.st.len[t];
-                P.slop = (u32)slop[i];
-                int rarest = 0;
-                for (int t = 1; t < Ti; t++) if (P.st.len[t] < P.st.len[rarest]) rarest = t;
-                P.anchor = 2 * (u64)P.st.len[rarest] >= N ? -1 : rarest;
-                const u64 slots = P.anchor >= 0 ? (u64)P.st.len[rarest] : N;
-                P.n_blocks = (u32)((slots + SA_SPAN_FD - 1) / SA_SPAN_FD);
-                djobs[Ti - 2].push_back(P);
-                drow[Ti - 2].push_back(i);
-                continue;
-            }
-        }
-        if (J.st.len[0] > (u32)SA_SPAN_SORT_MIN) continue;                         // (would be put in work order)
-        for (int t = 0; t < Ti; t++) J.st.off[t + 1] = J.st.off[t] + J.st.len[t];
-        for (int t = 0; t < Ti; t++) J.ck.coff[t + 1] = J.ck.coff[t] + sa_compact_chunks(J.st.len[t]);
-        for (int t = Ti; t < SA_SPAN_MAX_TERMS; t++) J.ck.coff[t + 1] = J.ck.coff[t];
-        J.n_chunks = J.ck.coff[Ti];
-        if (J.n_chunks == 0 || J.n_chunks > (u32)SA_SPAN_INLINE_SCAN) continue;
-        {
-            // header 0 in L?  (host arithmetic on the index's per-term edge flags, as in sa_span_counts_device)
-            const unsigned char e0 = ix->h_term_edge[terms[i][0]];
-            bool L = true;
-            for (int t = 1; t < Ti; t++) {
-                const unsigned char ei = ix->h_term_edge[terms[i][t]];
-                const bool a0 = e0 & 1, a0m = e0 & 2, bi = ei & 1, bim = ei & 2;
-                L &= (a0 && bi) || (bi && a0m) || (a0 && bim);
-            }
-            J.wrap_host = L ? 1 : 0;
-        }
-        // scratch of this phrase (offsets now, addresses once the buffer is known)
-        job_off.push_back(used);
-        take(SA_SPAN_CNT_WORDS * 4);
-        take(((size_t)2 * J.n_chunks + 8) * 4);
-        take(total_len + 64);
-        take(((size_t)J.st.len[0] + 64) * 4);                        // groups the fast pass abandons
-        for (int t = 0; t < Ti; t++) { take(((size_t)J.st.len[t] + 1) * 8); take(((size_t)J.st.len[t] + 1) * 4); take((size_t)J.st.len[t] + 1); }
+        J.st = sti;
+        sa_span_prefix(&J.st);
+        J.n_chunks = sa_span_chunk_tab(J.st, &J.ck);
+        if (J.n_chunks == 0 || J.n_chunks > (u32)SA_SPAN_INLINE_SCAN) continue;    // (would need the separate chunk scan)
+        J.wrap_host = sa_span_header0_in_L(ix, terms[i], Ti) ? 1 : 0;
+        job_off.push_back(pool.used);
+        job_buffers(pool, J);
         J.mp.T = Ti; J.mp.slop = (u32)slop[i]; J.mp.n_docs = N;
-        J.g_flags = std::min<u32>(16384u, J.st.off[Ti] / 256u + 1u);
+        J.g_flags = std::min<u32>(16384u, J.st.off[Ti] / 256u + 1u);  // (no block per 4096 documents: the pool's vectors are zero already)
         J.g_chunks = std::min<u32>(16384u, J.n_chunks);
         J.g_flat = (J.st.len[0] + 63u) / 64u;
         J.g_wave = std::min<u32>(128u, J.st.len[0]);                // (the fast pass abandons a few per cent of the groups at most; the blocks stride)
@@ -2401,7 +2423,7 @@ int sa_span_counts_batch(sa_index* ix, hipStream_t st, int n, const u32* const* 
     size_t n_slots = 0;
     for (int c = 0; c < 3; c++) for (const SpanDocParams& P : djobs[c]) n_slots += (P.n_blocks + 7u) >> 3;
     const size_t jobs_bytes = span_jobs_bytes + rank_jobs_bytes + doc_jobs_bytes + ((n_slots * sizeof(SpanSlot) + 255) & ~(size_t)255);
-    const size_t need = jobs_bytes + used + 4096;
+    const size_t need = jobs_bytes + pool.used + 4096;
     if (ix->span_batch_bytes < need) {
         SA_HIP(hipStreamSynchronize(st));
         if (ix->d_span_batch) SA_HIP(hipFree(ix->d_span_batch));
@@ -2440,27 +2462,13 @@ int sa_span_counts_batch(sa_index* ix, hipStream_t st, int n, const u32* const* 
     int class_first[5] = {0, 0, 0, 0, 0};
     for (int q = 0; q < nj; q++) {
         const int j = order[(size_t)q];
-        SpanJob J = jobs[(size_t)j];
-        size_t o = job_off[(size_t)j];
-        auto next = [&](size_t bytes) { char* p = base + o; o += (bytes + 255) & ~(size_t)255; return p; };
-        const int Ti = J.st.T;
+        SpanJob& J = hj[q];
+        J = jobs[(size_t)j];
+        SpanBump b = {base, job_off[(size_t)j]};
+        job_buffers(b, J);
         float* running = ix->d_span_counts + (size_t)q * cstride;
-        J.cnt = (u32*)next(SA_SPAN_CNT_WORDS * 4);
-        J.chunks = (u32*)next(((size_t)2 * J.n_chunks + 8) * 4);
-        J.flags = (unsigned char*)next((size_t)J.st.off[Ti] + 64);
-        u32* over_list = (u32*)next(((size_t)J.st.len[0] + 64) * 4);
-        for (int t = 0; t < Ti; t++) {
-            u64* cand = (u64*)next(((size_t)J.st.len[t] + 1) * 8);
-            u32* heads = (u32*)next(((size_t)J.st.len[t] + 1) * 4);
-            J.co.cand[t] = cand; J.co.heads[t] = heads;
-            J.co.gpos[t] = (unsigned char*)next((size_t)J.st.len[t] + 1);
-            J.mp.cand[t] = cand; J.mp.n_cand[t] = J.cnt + t; J.mp.heads[t] = heads; J.mp.n_heads[t] = J.cnt + SA_SPAN_MAX_TERMS + t;
-        }
         J.mp.fcounts = running;
         J.mp.touched = (unsigned char*)(running + cvec); J.mp.touch_shift = rank_tile_shift;
-        J.mp.over_list = over_list; J.mp.over_cnt = J.cnt + 4 * SA_SPAN_MAX_TERMS;
-        J.mp.in_list = over_list; J.mp.in_cnt = J.cnt + 4 * SA_SPAN_MAX_TERMS;
-        hj[q] = J;
         hr[q].counts = running; hr[q].touched = (unsigned char*)(running + cvec);
         hr[q].idf = idf[job_row[(size_t)j]]; hr[q].row = rows[job_row[(size_t)j]];
         d_out[job_row[(size_t)j]] = running;
@@ -2544,17 +2552,13 @@ int sa_span_counts_batch(sa_index* ix, hipStream_t st, int n, const u32* const* 
         }
         const u32 nb = (u32)(b - a);
         const SpanJob* jc = dj + a;
-        switch (c) {
-        case 0: hipLaunchKernelGGL(sa_k_span_flags_multi<2>, dim3(gf, nb), dim3(256), 0, st, jc); break;
-        case 1: hipLaunchKernelGGL(sa_k_span_flags_multi<3>, dim3(gf, nb), dim3(256), 0, st, jc); break;
-        case 2: hipLaunchKernelGGL(sa_k_span_flags_multi<4>, dim3(gf, nb), dim3(256), 0, st, jc); break;
-        default: hipLaunchKernelGGL(sa_k_span_flags_multi<0>, dim3(gf, nb), dim3(256), 0, st, jc); break;
-        }
+        const int Tc = hj[a].st.T;                                  // (2, 3 or 4 terms; the last class: more -- the tables' "any number")
+        sa_span_flags_by_terms(Tc, [&](auto tt) { hipLaunchKernelGGL(sa_k_span_flags_multi<decltype(tt)::value>, dim3(gf, nb), dim3(256), 0, st, jc); });
         hipLaunchKernelGGL(sa_k_span_compact_count_multi, dim3(gc, nb), dim3(SA_CT), 0, st, jc);
         hipLaunchKernelGGL(sa_k_span_compact_emit_multi, dim3(gc, nb), dim3(SA_CT), 0, st, jc);
-        if (c == 0) hipLaunchKernelGGL((sa_k_span_machine_flat_multi<SA_SPAN_LDS, SA_SPAN_PMAX, 2>), dim3(gl, nb), dim3(64), 0, st, jc);
-        else if (c == 1) hipLaunchKernelGGL((sa_k_span_machine_flat_multi<20, 20, 3>), dim3(gl, nb), dim3(64), 0, st, jc);
-        else hipLaunchKernelGGL((sa_k_span_machine_flat_multi<20, 20, 0>), dim3(gl, nb), dim3(64), 0, st, jc);
+        sa_span_flat_by_terms(Tc, [&](auto ce, auto pm, auto tt) {
+            hipLaunchKernelGGL((sa_k_span_machine_flat_multi<decltype(ce)::value, decltype(pm)::value, decltype(tt)::value>), dim3(gl, nb), dim3(64), 0, st, jc);
+        });
         hipLaunchKernelGGL(sa_k_span_machine_wave_multi, dim3(gw, nb), dim3(64), 0, st, jc);
     }
     for (int c = 0; c < 3; c++) {
@@ -2571,16 +2575,10 @@ int sa_span_counts_batch(sa_index* ix, hipStream_t st, int n, const u32* const* 
         const long long tw = sa_opt(ix->opts.span_tab_waves, dblocks[c] > 4u * (u32)ix->n_cus ? SA_SPAN_NTAB_BATCH : SA_SPAN_NTAB);
         const bool few = tw < SA_SPAN_NTAB;
         if (sa_opt(ix->opts.trace, 0)) fprintf(stderr, "sa_span_counts_batch: doc-parallel launch of %u phrases, %u blocks, %d table waves per block\n", cnt, dblocks[c], few ? SA_SPAN_NTAB_BATCH : SA_SPAN_NTAB);
-        if (c == 0) {
-            if (few) hipLaunchKernelGGL((sa_k_span_doc_fused_multi<2, SA_SPAN_NTAB_BATCH>), dim3(dblocks[c]), dim3(SA_SPAN_FT), pad, st, jc, wc);
-            else hipLaunchKernelGGL((sa_k_span_doc_fused_multi<2, SA_SPAN_NTAB>), dim3(dblocks[c]), dim3(SA_SPAN_FT), pad, st, jc, wc);
-        } else if (c == 1) {
-            if (few) hipLaunchKernelGGL((sa_k_span_doc_fused_multi<3, SA_SPAN_NTAB_BATCH>), dim3(dblocks[c]), dim3(SA_SPAN_FT), pad, st, jc, wc);
-            else hipLaunchKernelGGL((sa_k_span_doc_fused_multi<3, SA_SPAN_NTAB>), dim3(dblocks[c]), dim3(SA_SPAN_FT), pad, st, jc, wc);
-        } else {
-            if (few) hipLaunchKernelGGL((sa_k_span_doc_fused_multi<4, SA_SPAN_NTAB_BATCH>), dim3(dblocks[c]), dim3(SA_SPAN_FT), pad, st, jc, wc);
-            else hipLaunchKernelGGL((sa_k_span_doc_fused_multi<4, SA_SPAN_NTAB>), dim3(dblocks[c]), dim3(SA_SPAN_FT), pad, st, jc, wc);
-        }
+        sa_span_doc_by_terms(c + 2, [&](auto tt) {
+            if (few) hipLaunchKernelGGL((sa_k_span_doc_fused_multi<decltype(tt)::value, SA_SPAN_NTAB_BATCH>), dim3(dblocks[c]), dim3(SA_SPAN_FT), pad, st, jc, wc);
+            else hipLaunchKernelGGL((sa_k_span_doc_fused_multi<decltype(tt)::value, SA_SPAN_NTAB>), dim3(dblocks[c]), dim3(SA_SPAN_FT), pad, st, jc, wc);
+        });
     }
     SA_HIP(hipGetLastError());
     return SA_OK;
@@ -2629,15 +2627,15 @@ extern "C" int sa_span_search(const uint64_t* posns, const uint64_t* lengths, in
     u64* d_words; u32 *d_counts, *d_cnt, *d_chunks, *d_heads;
     SA_TRY(bufs.take((void**)&d_words, (size_t)total * 8));
     SA_TRY(bufs.take((void**)&d_counts, ((size_t)n_docs + 1) * 4));
-    SA_TRY(bufs.take((void**)&d_cnt, 4 * SA_SPAN_MAX_TERMS * 4));
+    SA_TRY(bufs.take((void**)&d_cnt, SA_SPAN_CNT_OVER * 4));          // (the block up to OVER: no fast pass here)
     SA_TRY(bufs.take((void**)&d_heads, ((size_t)total + T) * 4));
     const size_t max_n = (size_t)(total > n_docs ? total : n_docs);
     SA_TRY(bufs.take((void**)&d_chunks, ((size_t)sa_compact_chunks((u32)max_n + 1) + 8) * 4));
     SA_HIP(hipMemcpyAsync(d_words, posns + lengths[0], (size_t)total * 8, hipMemcpyHostToDevice, st));
     SA_HIP(hipMemsetAsync(d_counts, 0, ((size_t)n_docs + 1) * 4, st));
-    u32 h_cnt[4 * SA_SPAN_MAX_TERMS];
+    u32 h_cnt[SA_SPAN_CNT_OVER];
     memset(h_cnt, 0, sizeof(h_cnt));
-    for (int t = 0; t < T; t++) h_cnt[t] = (u32)(lengths[t + 1] - lengths[t]);
+    for (int t = 0; t < T; t++) h_cnt[SA_SPAN_CNT_NCAND + t] = (u32)(lengths[t + 1] - lengths[t]);
     SA_HIP(hipMemcpyAsync(d_cnt, h_cnt, sizeof(h_cnt), hipMemcpyHostToDevice, st));
     u32 G = (h_cnt[0] + 63u) & ~63u;
     u32 g_max = SA_SPAN_THREADS;
@@ -2655,12 +2653,12 @@ extern "C" int sa_span_search(const uint64_t* posns, const uint64_t* lengths, in
     mp.counts = d_counts; mp.n_docs = n_docs; mp.n_threads = G;
     for (int t = 0; t < T; t++) {
         const u64 off = lengths[t] - lengths[0];
-        mp.cand[t] = d_words + off; mp.n_cand[t] = d_cnt + t;
-        mp.heads[t] = d_heads + off + t; mp.n_heads[t] = d_cnt + SA_SPAN_MAX_TERMS + t;
+        mp.cand[t] = d_words + off; mp.n_cand[t] = d_cnt + SA_SPAN_CNT_NCAND + t;
+        mp.heads[t] = d_heads + off + t; mp.n_heads[t] = d_cnt + SA_SPAN_CNT_NHEADS + t;
         if (h_cnt[t] == 0) continue;
         DocHeads dh;
         dh.words = d_words + off; dh.out = d_heads + off + t;
-        sa_compact(dh, (const u32*)nullptr, h_cnt[t], d_chunks, d_cnt + SA_SPAN_MAX_TERMS + t, st);
+        sa_compact(dh, (const u32*)nullptr, h_cnt[t], d_chunks, d_cnt + SA_SPAN_CNT_NHEADS + t, st);
     }
     hipLaunchKernelGGL(sa_k_span_machine, dim3(G / 64), dim3(64), 0, st, mp);
     u64 *d_docs, *d_incr;
@@ -2668,10 +2666,10 @@ extern "C" int sa_span_search(const uint64_t* posns, const uint64_t* lengths, in
     SA_TRY(bufs.take((void**)&d_docs, n_hit_max * 8));
     SA_TRY(bufs.take((void**)&d_incr, n_hit_max * 8));
     NonZeroCounts nz; nz.counts = d_counts; nz.docs = d_docs; nz.incr = d_incr;
-    sa_compact(nz, (const u32*)nullptr, (u32)n_docs, d_chunks, d_cnt + 3 * SA_SPAN_MAX_TERMS, st);
+    sa_compact(nz, (const u32*)nullptr, (u32)n_docs, d_chunks, d_cnt + SA_SPAN_CNT_FILTER, st);
     SA_HIP(hipGetLastError());
     u32 n = 0;
-    SA_HIP(hipMemcpyAsync(&n, d_cnt + 3 * SA_SPAN_MAX_TERMS, 4, hipMemcpyDeviceToHost, st));
+    SA_HIP(hipMemcpyAsync(&n, d_cnt + SA_SPAN_CNT_FILTER, 4, hipMemcpyDeviceToHost, st));
     SA_HIP(hipStreamSynchronize(st));
     if (n) {
         SA_HIP(hipMemcpy(docs_out, d_docs, (size_t)n * 8, hipMemcpyDeviceToHost));

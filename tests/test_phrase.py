@@ -416,6 +416,52 @@ def test_slop_doc_parallel_route(api, seed, monkeypatch, capfd):
     dev.close()
 
 
+def test_slop_batch_takes_the_doc_parallel_route_exactly_when_the_phrase_alone_does(api, monkeypatch, capfd):
+    """One rule (sa_spans.hip: sa_span_doc_route_ok) decides the doc-parallel route for a phrase on its own and for the
+    phrases of a batch.  Cases on both sides of each edge of it -- T + slop = 15, T = 4, header 0 in L or not for three
+    terms (doc 0 holds terms 0..2 early and terms 3..5 only from position 40 on), an unknown term: the batch's
+    doc-parallel launches take as many phrases as went doc-parallel alone, and counts and top-k are the oracle's."""
+    import re
+    set_opt("trace", "1")
+    n_docs, vocab, k = 500, 6, 8
+    t, d, p, lens = synth.corpus_triples(n_docs, vocab, 20, seed=61)
+    keep = ~((d == 0) & (p < 40) & (t >= 3))
+    t, d, p = t[keep], d[keep], p[keep]
+    at = int(p[d == 0].max()) + 1
+    t = np.concatenate([t, [0, 1, 2]]); d = np.concatenate([d, [0, 0, 0]]); p = np.concatenate([p, [at, at + 1, at + 2]])
+    lens[0] = at + 3
+    order = np.lexsort((p, d, t))
+    t, d, p = t[order], d[order], p[order]
+    words, wt = rz.encode_sorted(t, d, p)
+    dev = DeviceIndex(words, rz.term_offsets(wt, vocab), lens, tile_docs=1024, api=api)
+    orc = O.OracleIndex.from_triples(t, d, p, n_docs, doc_lens=lens)
+    cases = [([0, 1], 13), ([0, 1], 14), ([0, 1, 2], 2), ([3, 4, 5], 2), ([3, 4, 5, 0], 11), ([3, 4, 5, 0], 12),
+             ([3, 4, 5, 0, 1], 2), ([1, vocab + 3], 2), ([4, 3], 1), ([2, 1, 0], 12), ([5, 0, 1], 13)]
+    alone = 0
+    for ph, slop in cases:
+        want = orc.phrase_freqs(ph, slop=slop)
+        capfd.readouterr()
+        got = dev.phrase_freqs_dense(ph, slop=slop)
+        err = capfd.readouterr().err
+        assert np.array_equal(got, want), (ph, slop)
+        alone += "slop route: doc-parallel" in err
+    pb = dev.phrase_batch([ph for ph, _ in cases], k=k, slop=[s for _, s in cases])
+    capfd.readouterr()
+    pb.run()
+    ps, pd_ = pb.fetch()
+    err = capfd.readouterr().err
+    pb.close()
+    in_batch = sum(int(x) for x in re.findall(r"doc-parallel launch of (\d+) phrases", err))
+    for i, (ph, slop) in enumerate(cases):
+        ws, wd = O.topk(orc.score(list(ph), slop=slop), k)
+        n = int((ws > 0).sum())
+        assert np.array_equal(ps[i, :n], ws[:n]) and np.array_equal(pd_[i, :n], wd[:n]), f"phrase {ph} slop {slop}"
+    print(f"doc-parallel alone: {alone} of {len(cases)}, in the batch: {in_batch}")
+    assert in_batch == alone, (in_batch, alone, err)
+    assert 0 < alone < len(cases), alone
+    dev.close()
+
+
 @pytest.mark.parametrize("seed", range(3))
 def test_slop_five_to_eight_terms(api, seed, monkeypatch, on_emu):
     """phrases of more terms than the span kernels are specialised for (flags: 2-4 terms; the fast pass requests the

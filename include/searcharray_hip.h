@@ -430,6 +430,25 @@ int sa_batch_set_filter(sa_batch_t* batch, sa_filter_t* filter);
  * SA_ERR_UNSUPPORTED: phrase batches; the timing option no_topk; an index whose tile size has no counting kernels (they exist for 1024,
  * 2048, 4096 and 8192 docs per tile).  The query-set queue (Part 2c) has no such call. */
 int sa_batch_set_min_match(sa_batch_t* batch, const uint32_t* min_match);
+/* OCCUR CLASSES (Lucene SHOULD / MUST / MUST_NOT, the `+tok` / `-tok` of Solr queries) for BM25 batches.  occur: n_queries x
+ * n_query_terms bytes in CALLER order, one per query slot: 0 should (optional), 1 must (required), 2 must_not (prohibited); another value
+ * -> SA_ERR_ARG; NULL clears them (all slots optional).  Query i then keeps only the documents that match EVERY required slot, NO
+ * prohibited slot and at least m of the OPTIONAL slots, m being the query's sa_batch_set_min_match value (0 without one: m counts optional
+ * slots only, as Lucene's minimumShouldMatch); every other document scores 0.  "Matches" is the one definition of sa_batch_set_min_match:
+ * the slot's own contribution fl(factor x weight) is > 0.  A kept document's score is the sum over its non-prohibited slots in slot order,
+ * bit for bit that of the plain disjunction of those slots: a prohibited slot adds nothing.  A document needs a positive score to appear,
+ * so a query of prohibited slots only returns nothing.  Unknown terms and padding never match: under must -> no hits for that query;
+ * under must_not -> no effect.  A term given twice is two slots, each with its own class.  With a filter as well a document must pass
+ * both tests.
+ * The contract of sa_batch_set_min_match: applies from the next run on, including runs of the query set already loaded; persists across
+ * sa_batch_reset / sa_batch_step -- slot j of row i of every later query set gets class [i][j].
+ * Route: a batch with any slot that is not optional runs on the per-query tile kernels' occur instantiations only (sa_batch_last_route
+ * says 0 whatever the options say), without starting bounds (sa_batch_seeds reports 0).  A tile in which a required term has no postings,
+ * fewer than m optional terms have any, or only prohibited terms have any, is skipped before a posting is read (counted by
+ * sa_batch_stats like the minimum-should-match skips).  A batch whose slots are all optional runs exactly as without the call.
+ * SA_ERR_UNSUPPORTED: phrase batches; the timing option no_topk; an index whose tile size has no counting kernels.  The query-set queue
+ * (Part 2c) has no such call. */
+int sa_batch_set_occur(sa_batch_t* batch, const uint8_t* occur);
 
 /* ---- Part 2c: a query-set QUEUE (csrc/sa_queue.hip).  A ring of `depth` batches of the same shape behind one handle, fed by a WORKER
  * THREAD of the library: sa_queue_submit copies a set of B x T term ids (weights come from the index's idf table, sa_index_set_idf_table,
@@ -604,6 +623,9 @@ int sa_sharded_batch_set_filter(sa_sharded_batch_t* batch, sa_sharded_filter_t* 
 /* sa_batch_set_min_match with the same n_queries values on every shard's batch (NULL clears): the count is per document and shards are
  * doc ranges */
 int sa_sharded_batch_set_min_match(sa_sharded_batch_t* batch, const uint32_t* min_match);
+/* sa_batch_set_occur with the same n_queries x n_query_terms classes on every shard's batch (NULL clears): each shard applies them to
+ * its own docs before the exchange */
+int sa_sharded_batch_set_occur(sa_sharded_batch_t* batch, const uint8_t* occur);
 
 /* ------------------------------------------------------------------------------------- */
 /* Part 4 -- dense vectors on the device: the combine step of Solr-style multi-field queries */

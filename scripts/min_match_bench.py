@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""What minimum-should-match costs and saves on the headline workload (bench.py's shape): 10 M synthetic Zipf docs, 256 x 4-term
+"""What minimum-should-match and occur classes (+tok / -tok) cost and save on the headline workload (bench.py's shape): 10 M synthetic Zipf docs, 256 x 4-term
 BASELINE-shaped queries at k = 10, fresh rotating query sets stepped through a ring of batches (one sa_batch_step + fetch per step).
 
   python scripts/min_match_bench.py [--parent-lib PATH] [--out profiles/min_match.jsonl]
@@ -13,6 +13,10 @@ Legs (each warmed; a leg's time is the median of `--regions` regions of `--steps
                         region in one process: the spread between b1 and b2 is the margin b is judged by -- a larger gap would mean
                         that the compile-time switch leaked into the old instantiations)
   skipped               share of the (tile, query) items the popcount shortcut left before reading a posting (sa_batch_stats)
+  o/-t0, o/+t0, o/+t0-t1  occur classes on every query (sa_batch_set_occur), default options: slot 0 prohibited; slot 0 required; slot 0
+                        required and slot 1 prohibited -- each beside p/plain and p/m=2, the PARENT build's plain batch (default
+                        options) and its minimum-should-match batch (--parent-lib; without it this build's, marked so), alternating
+                        region by region in one process
   c                     what a caller had before: edismax_search per query over a one-column frame of the same documents with the
                         same mm (`--edismax-queries` queries; the rows it returns must be those of leg a)
 Every a / b leg's results are compared with the oracle on `--check` queries of set 0."""
@@ -77,31 +81,42 @@ def main():
         out.write(line + "\n")
         out.flush()
 
-    def verify(stream, values):
+    def verify(stream, values, occur=None):
         scores, docs = stream.results[0]
         for qi, per in enumerate(per0):
-            dense = np.sum(per, axis=0)
             m = 0 if values is None else int(values[qi])
-            if m > 1:
-                dense[np.sum([s > 0 for s in per], axis=0) < m] = 0
+            if occur is None:
+                dense = np.sum(per, axis=0)
+                if m > 1:
+                    dense[np.sum([s > 0 for s in per], axis=0) < m] = 0
+            else:                                                # (0 should, 1 must, 2 must_not; m counts the should slots)
+                cl = [int(c) for c in occur[qi]]
+                dense = np.sum([np.zeros_like(s) if c == 2 else s for s, c in zip(per, cl)], axis=0)
+                ok = np.sum([s > 0 for s, c in zip(per, cl) if c == 0] or [np.zeros(D, dtype=bool)], axis=0) >= m
+                for s, c in zip(per, cl):
+                    ok &= (s > 0) if c == 1 else ~(s > 0) if c == 2 else True
+                dense[~ok] = 0
             ws, wd = O.topk(dense, K)
             n = int((ws > 0).sum())
             if not (np.array_equal(scores[qi, :n], ws[:n]) and np.array_equal(docs[qi, :n], wd[:n]) and not scores[qi, n:].any()):
                 return False
         return True
 
-    def leg(name, side, values=None, opts=None):
+    def leg(name, side, values=None, opts=None, occur=None):
         # a ring of its own per leg (Side.ring shares rings by options): no leg depends on the values another one left behind
         ring = [QueryBatch(side.index, sets[i % len(sets)], k=K, idf=side.idf_table[sets[i % len(sets)]], opts=opts or {}) for i in range(args.pipeline)]
         side.rings[(name, side.name)] = ring                     # (closed with the side)
-        if values is not None:                                   # (only legs of this build carry values: the parent has no such call)
+        if values is not None:
             for b in ring:
                 b.set_min_match(values)
+        if occur is not None:                                    # (only legs of this build carry classes: the parent has no such call)
+            for b in ring:
+                b.set_occur(occur)
         s = Stream(side, ring, sets)
         s.steps(max(args.warmup, 2 * args.pipeline))
-        s.values = values
+        s.values, s.occur = values, occur
         s.meta = {"leg": name, "lib": side.name, "k": K, "min_match": "none" if values is None else sorted(set(int(v) for v in values)),
-                  "options": opts or {}, "docs": D, "queries_per_step": B, "tile_docs": int(info.tile_docs)}
+                  "occur": "none" if occur is None else "".join("s+-"[int(c)] for c in occur[0]), "options": opts or {}, "docs": D, "queries_per_step": B, "tile_docs": int(info.tile_docs)}
         return s
 
     def measure(streams):
@@ -117,7 +132,7 @@ def main():
             med.append(float(np.median(ms)))
             emit(dict(s.meta, ms_per_step=round(med[-1], 4), ms_per_step_min=round(ms[0], 4), ms_per_step_max=round(ms[-1], 4),
                       queries_per_s=round(B / (med[-1] / 1e3)), route=s.ring[0].last_route(), seeds=bool(s.ring[0].seeds().any()),
-                      equals_oracle=verify(s, s.values), regions=args.regions, steps_per_region=args.steps))
+                      equals_oracle=verify(s, s.values, s.occur), regions=args.regions, steps_per_region=args.steps))
         return med
 
     tiles_only = {"stage": 0, "sparse": 0, "group": 0}
@@ -140,6 +155,14 @@ def main():
         skipped, _ = bt.stats(False)
         emit({"leg": "skipped", "min_match": m, "items": int(info.n_tiles) * B, "skipped": int(skipped), "share": round(skipped / (int(info.n_tiles) * B), 4)})
         bt.close()
+    # occur classes: each pattern beside the parent build's plain and minimum-should-match batches
+    base = sides[1] if args.parent_lib else new
+    base_name = "" if args.parent_lib else " (THIS build: no --parent-lib)"
+    T = sets[0].shape[1]
+    for name, cls in (("o/-t0", [2] + [0] * (T - 1)), ("o/+t0", [1] + [0] * (T - 1)), ("o/+t0-t1", [1, 2] + [0] * (T - 2))):
+        occ = np.tile(np.asarray(cls, dtype=np.uint8), (B, 1))
+        o_ms, p_ms, pm_ms = measure([leg(name, new, None, None, occ), leg(f"p/plain beside {name}{base_name}", base), leg(f"p/m=2 beside {name}{base_name}", base, [2] * B)])
+        emit({"leg": name, "ratio_to_parent_plain": round(o_ms / p_ms, 3), "ratio_to_parent_m2": round(o_ms / pm_ms, 3)})
     # c: edismax_search per query over a one-column frame of the same documents
     if args.edismax_queries:
         import pandas as pd

@@ -158,6 +158,8 @@ PROTOTYPES = {
     "sa_batch_set_min_match": (c_int, [c_void_p, u32p]),
     "sa_batch_row_order": (c_int, [c_void_p, u32p]),
     "sa_sharded_batch_set_min_match": (c_int, [c_void_p, u32p]),
+    "sa_batch_set_occur": (c_int, [c_void_p, POINTER(ctypes.c_uint8)]),
+    "sa_sharded_batch_set_occur": (c_int, [c_void_p, POINTER(ctypes.c_uint8)]),
     "sa_index_select_rows": (c_int, [c_void_p, u64p, c_uint64]),
     "sa_host_alloc": (c_int, [c_uint64, POINTER(c_void_p)]),
     "sa_host_free": (c_int, [c_void_p]),

@@ -44,8 +44,9 @@ static sa_plan sa_batch_plan(const sa_batch* bt, bool deferred, bool unpruned) {
     const bool filtered = bt->filter != nullptr;
     // A batch with minimum-should-match values > 1 (sa_batch_set_min_match) is stricter still: only the per-query tile kernels count the
     // slots a doc matched, so its route is SA_ROUTE_TILES whatever the options say -- never staged, grouped or dynamically pruned -- and
-    // it starts without the rank-table bounds, which count docs that the test may exclude.
-    const bool mm = bt->mm_on;
+    // it starts without the rank-table bounds, which count docs that the test may exclude.  The same holds for a batch with required or
+    // prohibited slots (sa_batch_set_occur): the terms' rank tables know nothing of exclusions.
+    const bool mm = bt->counting();
     // (the grouped kernel and the starting bounds need non-negative scores: the sign bit is a mark)
     pl.group = !mm && sa_opt(o.group, 1) != 0 && bt->weights_ok && sa_grouped_tiles(ix->tile_docs);   // (no row groups for a set that cannot take the overlay)
     pl.seed_wanted = bt->weights_ok && bt->impacts && bt->k <= 1024u && sa_opt(o.term_seed, 1) != 0 && sa_opt(o.sparse, -1) != 1;
@@ -273,7 +274,7 @@ static int sa_batch_alloc_bm25(sa_batch* bt) {
     bt->st_bytes = sa_stage_upload_bytes((u32)B, (u32)T);
     off = (off + 15) & ~(size_t)15;
     const size_t o_st = take(bt->st_bytes);
-    const size_t o_mm = take(B * 4);
+    const size_t o_mm = take(B * 4), o_occ = take(B * 8);
     SA_TRY(sa_batch_alloc_upload(bt, off));
     char* u = bt->d_up;
     bt->d_p1_off = (u64*)(u + o_p1); bt->d_bloom_off = (u64*)(u + o_boff);
@@ -284,6 +285,7 @@ static int sa_batch_alloc_bm25(sa_batch* bt) {
     bt->d_seed = (u32*)(u + o_seed);
     bt->d_st = u + o_st;
     bt->d_min_match = (u32*)(u + o_mm);              // (behind d_terms: Bm25Params::min_match_off)
+    bt->d_occur = (u32*)(u + o_occ);                 // (likewise: Bm25Params::occur_off)
     {
         std::vector<u32> iota(B);
         for (u32 i = 0; i < B; i++) iota[i] = i;
@@ -640,13 +642,18 @@ static int sa_batch_fill(sa_batch* bt, const uint32_t* terms, const float* idf) 
     {                                                           // minimum-should-match: row r gets the value of caller query perm[r]
         u32* h_mm = (u32*)at(bt->d_min_match);
         for (u32 r = 0; r < B; r++) h_mm[r] = bt->min_match.empty() ? 0u : bt->min_match[bt->perm[r]];
+        u32* h_occ = (u32*)at(bt->d_occur);                     // ... and its occur masks (required, prohibited)
+        for (u32 r = 0; r < B; r++) {
+            h_occ[2 * r] = bt->occur.empty() ? 0u : bt->occur[2 * (size_t)bt->perm[r]];
+            h_occ[2 * r + 1] = bt->occur.empty() ? 0u : bt->occur[2 * (size_t)bt->perm[r] + 1];
+        }
     }
     memset(h_grpd, 0, (size_t)3 * B * sizeof(u32));
     if (!h_grp.empty()) memcpy(h_grpd, h_grp.data(), h_grp.size() * sizeof(u32));     // (at most B groups)
     memset(at(bt->d_seed), 0, (size_t)B * sizeof(u32));
     if (pl.seed_wanted) sa_impacts_ensure_topf(ix, bt->impacts.get());
     const bool tables = pl.seed_wanted && bt->impacts->d_topf;   // the rank tables and the terms' largest factors exist
-    bt->seed_on = tables && !bt->filter && !bt->mm_on;          // (a filtered or minimum-should-match set starts from 0: the tables' bounds count docs the test may exclude)
+    bt->seed_on = tables && !bt->filter && !bt->counting();     // (a filtered, minimum-should-match or occur set starts from 0: the tables' bounds count docs the test may exclude)
     // the staged-tile route's plan (sa_stage.hip): distinct terms, per-query bound tables and the starting bounds, formed on the
     // host into the same upload.  A set that has one does not need the slice table: sa_k_make_bounds is left out of the step and
     // only runs if the run takes another route after all (sa_batch_ensure_bounds)
@@ -654,7 +661,7 @@ static int sa_batch_fill(sa_batch* bt, const uint32_t* terms, const float* idf) 
     bt->st_dir.reset();
     bt->st_slices.clear();
     // (a filtered set is planned with zero starting bounds: every term staged, none probed)
-    if (tables && pl.stage_wanted && !bt->mm_on) SA_TRY(sa_stage_plan(bt, img, h_terms, h_idf));
+    if (tables && pl.stage_wanted && !bt->counting()) SA_TRY(sa_stage_plan(bt, img, h_terms, h_idf));
     // the pruning tables: now, if the run will prune (the route rule, now that the groups and the staged plan are known); else on demand
     if (sa_batch_plan(bt, true, false).route == SA_ROUTE_PRUNED) sa_batch_fill_prune_tables(bt, img);
     else { bt->sparse_ok = false; bt->bloom_bytes = 0; bt->sparse_p1_total = 0; bt->sparse_p2_max = 0; }
@@ -791,6 +798,45 @@ extern "C" int sa_batch_set_min_match(sa_batch_t* bt, const uint32_t* min_match)
     return sa_batch_refill(bt);
 }
 
+// Occur classes: from its next run on, slot j of caller query i is optional (0), required (1) or prohibited (2) -- occur[i * T + j];
+// null: all optional, as before.  The contract of sa_batch_set_min_match, whose values then count the optional slots.
+extern "C" int sa_batch_set_occur(sa_batch_t* bt, const uint8_t* occur) {
+    SA_ARG(bt && bt->ix, "null batch");
+    if (bt->kind != 0) { sa_set_error("sa_batch_set_occur: phrase batches do not take occur classes"); return SA_ERR_UNSUPPORTED; }
+    sa_index* ix = bt->ix;
+    std::lock_guard<std::mutex> g(ix->mu);
+    SA_HIP(hipSetDevice(ix->device));
+    const u32 B = bt->B, T = bt->T;                             // (T <= 32, sa_batch_create: a mask has a bit per slot)
+    std::vector<u32> masks;
+    u32 n_must = 0, n_not = 0;
+    if (occur) {
+        masks.assign((size_t)2 * B, 0u);
+        for (u32 i = 0; i < B; i++)
+            for (u32 j = 0; j < T; j++) {
+                const uint8_t c = occur[(size_t)i * T + j];
+                SA_ARG(c <= 2, "occur classes are 0 (should), 1 (must) and 2 (must_not)");
+                if (c) masks[2 * (size_t)i + (c - 1u)] |= 1u << j;
+                n_must += c == 1; n_not += c == 2;
+            }
+    }
+    const bool on = n_must + n_not != 0;
+    if (on && sa_opt(bt->opts.no_topk, 0) != 0) { sa_set_error("sa_batch_set_occur: not with the timing option no_topk"); return SA_ERR_UNSUPPORTED; }
+    if (on && !sa_min_match_tiles(ix->tile_docs)) {
+        sa_set_error("sa_batch_set_occur: no counting kernel for tile_docs %u (1024, 2048, 4096, 8192)", ix->tile_docs);
+        return SA_ERR_UNSUPPORTED;
+    }
+    if (!occur && bt->occur.empty()) return SA_OK;
+    // (as in sa_batch_reset: an unfetched run that was flagged is redone first -- with the classes and the tables it ran with)
+    if (bt->res_pending && bt->unfetched) {
+        SA_HIP(hipEventSynchronize(bt->ev_res));
+        SA_TRY(sa_batch_redo_if_flagged(bt));
+    }
+    bt->occur.swap(masks);
+    bt->occur_on = on;
+    if (sa_opt(bt->opts.trace, 0)) fprintf(stderr, "sa_batch_set_occur: %u required and %u prohibited slots in %u queries\n", n_must, n_not, B);
+    return sa_batch_refill(bt);
+}
+
 extern "C" int sa_index_set_idf_table(sa_index_t* ix, const float* idf_per_term, uint32_t n_terms) {
     SA_ARG(ix && (idf_per_term || n_terms == 0), "null argument");
     SA_ARG(n_terms == ix->n_terms, "one idf per term of the index");
@@ -882,7 +928,8 @@ static Bm25Params sa_batch_params(const sa_batch* bt, const sa_plan& pl) {
     p.seed = pl.seed ? bt->d_seed : nullptr;
     p.qlist = nullptr; p.nq = bt->B;
     if (bt->filter) { p.filt = bt->filter->d_words; p.filt_blk = bt->filter->d_blk; p.filt_nblk = bt->filter->n_blocks; }
-    if (bt->mm_on) { p.min_match_off = (u32)((const char*)bt->d_min_match - (const char*)bt->d_terms); p.stats = bt->d_stats; }     // (sa_batch_stats then counts the (tile, query) items skipped)
+    if (bt->counting()) { p.min_match_off = (u32)((const char*)bt->d_min_match - (const char*)bt->d_terms); p.stats = bt->d_stats; }     // (sa_batch_stats then counts the (tile, query) items skipped)
+    if (bt->occur_on) p.occur_off = (u32)((const char*)bt->d_occur - (const char*)bt->d_terms);
     return p;
 }
 
@@ -970,6 +1017,11 @@ static int sa_batch_run_bm25(sa_batch* bt, u64* shard_out, bool deferred, bool u
         u32 n = 0;
         for (u32 v : bt->min_match) n += v > 1u ? 1u : 0u;
         fprintf(stderr, "sa_batch: minimum-should-match run: %u of %u queries with a value > 1: %s\n", n, bt->B, pl.pruned ? "per-query tile kernel" : "per-query tile kernel, unpruned");
+    }
+    if (bt->occur_on && sa_opt(bt->opts.trace, 0)) {
+        u32 n = 0;
+        for (u32 i = 0; i < bt->B; i++) n += (bt->occur[2 * (size_t)i] | bt->occur[2 * (size_t)i + 1]) ? 1u : 0u;
+        fprintf(stderr, "sa_batch: occur run: %u of %u queries with a required or prohibited slot: %s\n", n, bt->B, pl.pruned ? "per-query tile kernel" : "per-query tile kernel, unpruned");
     }
     sa_batch_clear_state(bt, pl.pruned, pl.route == SA_ROUTE_PRUNED);
     const u32 slot = bt->ev_n % SA_EVENT_RING;

@@ -61,6 +61,14 @@ struct sa_batch {
     std::vector<u32> min_match;
     bool mm_on = false;
     u32* d_min_match = nullptr;     // [B] in the upload block
+    // occur classes (sa_batch_set_occur): per CALLER query the masks of its required and its prohibited slots (bit j: slot j), [B][2];
+    // empty: none set.  Written by every fill in device-row order like the values above (d_occur).  occur_on: some slot is not
+    // optional -- the batch then takes the restrictions of mm_on (counting()), on the instantiations that keep the classes apart,
+    // and min_match counts the optional slots only
+    std::vector<u32> occur;
+    bool occur_on = false;
+    u32* d_occur = nullptr;         // [B][2] in the upload block
+    bool counting() const { return mm_on || occur_on; }
     // Everything a NEW set of queries changes on the device is one contiguous UPLOAD BLOCK (d_up) with a
     // page-locked host image: sa_batch_reset fills the image and enqueues ONE hipMemcpyAsync (+ the slice-table
     // kernel) -- no allocation, no blocking copy, no synchronisation.  The pointers below (d_terms ... d_bloom_off

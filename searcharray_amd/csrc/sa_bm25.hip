@@ -407,9 +407,22 @@ __host__ __device__ constexpr int sa_tile_tab_floats() {
 // than m slots are cleared BEFORE the filter clear and any selection, so everything downstream is unchanged.  A term phase touches a
 // doc at most once and phases are separated by barriers: the update is a plain byte read-modify-write (ds_read_u8 / ds_write_b8 --
 // byte stores of different lanes into one dword do not disturb each other).  The instantiations without MM contain none of it.
-template <int TILE, int THREADS, int MODE, bool IMP, bool MM = false>
+// MM == 2: occur classes as well (p.occur_off, sa_batch_set_occur): every slot of the query is optional, required or prohibited, and m
+// counts the optional ones.  The state per doc is 16 bits wide (SA_OCC_*): matched optional slots in bits 0-5, matched required slots in
+// bits 6-11, bit 12 set by a prohibited slot -- a slot's class is uniform for its phase, so the update keeps the shape of the byte's.
+// A prohibited slot is tested with its real product and not added at all (the same bits as adding it with weight 0: x + 0 is exact), so
+// its phase leaves the accumulators alone.  Tiles that cannot hold a doc that passes
+// are left like those of MM == 1; a doc stays when its state says  optional >= m, required == all of them, prohibited none.
+#define SA_OCC_SHOULD 1u
+#define SA_OCC_MUST 0x40u
+#define SA_OCC_NOT 0x1000u
+template <int MM> struct sa_match_state { typedef unsigned char type; };
+template <> struct sa_match_state<2> { typedef unsigned short type; };
+template <int TILE, int THREADS, int MODE, bool IMP, int MM = 0>
 __device__ __forceinline__ void sa_bm25_tile_item(const Bm25Params& p, const u32 tile, const u32 qi, u64* smem, float* s_tab,
-                                                  unsigned char* mc = nullptr) {
+                                                  typename sa_match_state<MM>::type* mc = nullptr) {
+    constexpr bool OCC = MM == 2;
+    typedef typename sa_match_state<MM>::type mc_t;
     constexpr int NW = THREADS / SA_WAVE;
     constexpr int E = TILE / THREADS;
     constexpr int CAP = (TILE >= 8192) ? 2048 : TILE / 4;      // candidate list capacity (MODE 0)
@@ -480,14 +493,34 @@ __device__ __forceinline__ void sa_bm25_tile_item(const Bm25Params& p, const u32
         if (!any) todo = 0u;
     }
     u32 mm = 0;                                                 // (uniform) slots a doc of this query must match
-    if constexpr (MM) {
+    u32 o_must = 0, o_not = 0, n_must = 0;                      // (uniform) the query's required / prohibited slots, MM == 2
+    if constexpr (MM != 0) {
         mm = ((const u32*)((const char*)p.terms + p.min_match_off))[q];
-        // fewer than mm of the query's terms have postings in this tile: no doc of it can match mm slots
-        if (todo != 0u && (u32)__builtin_popcount(todo) < mm) {
+        bool skip;
+        if constexpr (OCC) {
+            const u32* oc = (const u32*)((const char*)p.terms + p.occur_off) + 2u * q;
+            o_must = oc[0]; o_not = oc[1];
+            n_must = (u32)__builtin_popcount(o_must);
+            // a required term without postings in this tile, fewer than mm optional ones with postings, or prohibited ones only
+            skip = (todo & o_must) != o_must || (u32)__builtin_popcount(todo & ~(o_must | o_not)) < mm || (todo & ~o_not) == 0u;
+        } else {
+            // fewer than mm of the query's terms have postings in this tile: no doc of it can match mm slots
+            skip = (u32)__builtin_popcount(todo) < mm;
+        }
+        if (todo != 0u && skip) {
             todo = 0u;
             if (p.stats && tid == 0) atomicAdd(&p.stats[q], 1u);
         }
     }
+    // the state of a doc after a posting of a phase of class `cls` (SA_OCC_*; MM == 1: every slot counts one) whose product is `prod`
+    auto bump = [](u32 c, float prod, u32 cls) -> u32 {
+        if constexpr (OCC) return prod > 0.f ? ((c + (cls & (SA_OCC_NOT - 1u))) | (cls & SA_OCC_NOT)) : c;
+        else return c + (prod > 0.f ? 1u : 0u);
+    };
+    // a phase's postings are added to the accumulators (uniform; not those of a prohibited slot)
+    auto adds = [](u32 cls) -> bool { return cls != SA_OCC_NOT; };
+    // the state beside the accumulator at byte offset s
+    auto mc_at = [&](u32 s) -> mc_t& { return mc[s >> 2]; };
     auto lane64 = [](u64 x, u32 l) -> u64 {                      // value of lane l (wave-uniform l) in scalar registers
         const u32 a = (u32)__builtin_amdgcn_readlane((int)(u32)x, (int)l), b = (u32)__builtin_amdgcn_readlane((int)(u32)(x >> 32), (int)l);
         return ((u64)b << 32) | a;
@@ -502,7 +535,7 @@ __device__ __forceinline__ void sa_bm25_tile_item(const Bm25Params& p, const u32
     // Per posting: unpack, saturation-table lookup (or the arithmetic path for out-of-table
     // tf / dl), multiply by idf, and a read-modify-write of the doc's LDS accumulator.  One
     // posting per (term, doc): no two lanes of a term phase touch the same slot.
-    auto score_into = [&](u64 x, bool valid, float idf) {
+    auto score_into = [&](u64 x, bool valid, float idf, u32 cls) {
         const u32 d = (u32)((x >> SA_KEY_SHIFT) - tile_base);
         const u32 tfi = (u32)(x & SA_LSB_MASK);
         const u32 dli = (u32)((x >> SA_LSB_BITS) & SA_LSB_MASK);
@@ -517,8 +550,12 @@ __device__ __forceinline__ void sa_bm25_tile_item(const Bm25Params& p, const u32
                 sat = __fdiv_rn(tf, __fadd_rn(tf, norm));
             }
             const float prod = __fmul_rn(sat, idf);
-            acc[d] = __fadd_rn(acc[d], prod);
-            if constexpr (MM) mc[d] = (unsigned char)(mc[d] + (prod > 0.f ? 1u : 0u));
+            if constexpr (OCC) {
+                if (adds(cls)) acc[d] = __fadd_rn(acc[d], prod);
+            } else {
+                acc[d] = __fadd_rn(acc[d], prod);
+            }
+            if constexpr (MM != 0) mc[d] = (mc_t)bump(mc[d], prod, cls);
         }
     };
     // Impact stream: the factor is in the posting and a posting is valid iff its doc lies in this tile
@@ -558,10 +595,18 @@ __device__ __forceinline__ void sa_bm25_tile_item(const Bm25Params& p, const u32
         return b;
     };
     // impact stream: one pair per lane
-    auto score_pair = [&](const sa_u64x2& v, float idf) {
+    auto score_pair = [&](const sa_u64x2& v, float idf, u32 cls) {
         const u32 spare = ((u32)TILE + (tid & (u32)(SA_WAVE - 1))) * 4u;
         const u32 d0 = (u32)(v.x >> 32) - tile_base_b, d1 = (u32)(v.y >> 32) - tile_base_b;
         const u32 s0 = d0 < (u32)TILE * 4u ? d0 : spare, s1 = d1 < (u32)TILE * 4u ? d1 : spare;
+        if constexpr (OCC) {
+            if (!adds(cls)) {                                   // (uniform) a prohibited slot: the states only
+                const u32 c0 = mc_at(s0), c1 = mc_at(s1);
+                mc_at(s0) = (mc_t)bump(c0, __fmul_rn(__uint_as_float((u32)v.x), idf), cls);
+                mc_at(s1) = (mc_t)bump(c1, __fmul_rn(__uint_as_float((u32)v.y), idf), cls);
+                return;
+            }
+        }
         const float v0 = acc_at(s0), v1 = acc_at(s1);
         const float p0 = __fmul_rn(__uint_as_float((u32)v.x), idf);
         const float w0 = __fadd_rn(v0, p0);
@@ -569,20 +614,20 @@ __device__ __forceinline__ void sa_bm25_tile_item(const Bm25Params& p, const u32
         const float w1 = __fadd_rn(v1, p1);
         acc_at(s0) = w0;
         acc_at(s1) = w1;
-        if constexpr (MM) {                                     // (byte s >> 2 beside accumulator s; a sentinel's product is NaN: not > 0)
-            const u32 c0 = mc[s0 >> 2], c1 = mc[s1 >> 2];
-            mc[s0 >> 2] = (unsigned char)(c0 + (p0 > 0.f ? 1u : 0u));
-            mc[s1 >> 2] = (unsigned char)(c1 + (p1 > 0.f ? 1u : 0u));
+        if constexpr (MM != 0) {                                // (state s >> 2 beside accumulator s; a sentinel's product is NaN: not > 0)
+            const u32 c0 = mc_at(s0), c1 = mc_at(s1);
+            mc_at(s0) = (mc_t)bump(c0, p0, cls);
+            mc_at(s1) = (mc_t)bump(c1, p1, cls);
         }
     };
-    auto score_batch = [&](const Batch& b, u64 lo, u64 hi, u32 first, float idf) {
+    auto score_batch = [&](const Batch& b, u64 lo, u64 hi, u32 first, float idf, u32 cls) {
         const u64 a0 = lo & ~1ull;
         const u32 npairs = (hi > a0) ? (u32)((hi - a0 + 1) >> 1) : 0u;
         if constexpr (IMP) {
             const u32 spare = ((u32)TILE + (tid & (u32)(SA_WAVE - 1))) * 4u;
             if (first + (tid & ~(u32)(SA_WAVE - 1)) >= npairs) return;     // wave-uniform: no pair of this batch is this wave's
             if (npairs - first <= (u32)THREADS) {               // the last step of a slice (a short slice's only one)
-                score_pair(b.v[0], idf);
+                score_pair(b.v[0], idf, cls);
                 return;
             }
             // lanes / steps past the end of the slice hold sentinels
@@ -594,6 +639,26 @@ __device__ __forceinline__ void sa_bm25_tile_item(const Bm25Params& p, const u32
                 slot[2 * u] = d0 < (u32)TILE * 4u ? d0 : spare;
                 slot[2 * u + 1] = d1 < (u32)TILE * 4u ? d1 : spare;
             }
+            // the same batch of eight on the match states, all reads before all writes as below -- and behind the accumulators'
+            // stores, when the eight sums have left the registers (in front of them: 131 VGPRs, a wave per SIMD less)
+            auto states = [&]() {
+                u32 cnt[2 * PF];
+#pragma unroll
+                for (int i = 0; i < 2 * PF; i++) cnt[i] = mc_at(slot[i]);
+#pragma unroll
+                for (int u = 0; u < PF; u++) {
+                    cnt[2 * u] = bump(cnt[2 * u], __fmul_rn(__uint_as_float((u32)b.v[u].x), idf), cls);
+                    cnt[2 * u + 1] = bump(cnt[2 * u + 1], __fmul_rn(__uint_as_float((u32)b.v[u].y), idf), cls);
+                }
+#pragma unroll
+                for (int i = 0; i < 2 * PF; i++) mc_at(slot[i]) = (mc_t)cnt[i];
+            };
+            if constexpr (OCC) {
+                if (!adds(cls)) {                               // (uniform) a prohibited slot: the states only
+                    states();
+                    return;
+                }
+            }
 #pragma unroll
             for (int i = 0; i < 2 * PF; i++) val[i] = acc_at(slot[i]);
 #pragma unroll
@@ -603,20 +668,7 @@ __device__ __forceinline__ void sa_bm25_tile_item(const Bm25Params& p, const u32
             }
 #pragma unroll
             for (int i = 0; i < 2 * PF; i++) acc_at(slot[i]) = val[i];
-            // the same batch of eight on the count bytes, all reads before all writes as above -- and behind the accumulators'
-            // stores, when the eight sums have left the registers (in front of them: 131 VGPRs, a wave per SIMD less)
-            if constexpr (MM) {
-                u32 cnt[2 * PF];
-#pragma unroll
-                for (int i = 0; i < 2 * PF; i++) cnt[i] = mc[slot[i] >> 2];
-#pragma unroll
-                for (int u = 0; u < PF; u++) {
-                    cnt[2 * u] += __fmul_rn(__uint_as_float((u32)b.v[u].x), idf) > 0.f ? 1u : 0u;
-                    cnt[2 * u + 1] += __fmul_rn(__uint_as_float((u32)b.v[u].y), idf) > 0.f ? 1u : 0u;
-                }
-#pragma unroll
-                for (int i = 0; i < 2 * PF; i++) mc[slot[i] >> 2] = (unsigned char)cnt[i];
-            }
+            if constexpr (MM != 0) states();
             return;
         }
         const u32 r_lo = (u32)(lo - a0), r_hi = (u32)(hi - a0);     // the slice inside its hull
@@ -626,8 +678,8 @@ __device__ __forceinline__ void sa_bm25_tile_item(const Bm25Params& p, const u32
             const u32 jw = first + (u32)u * THREADS + (tid & ~(u32)(SA_WAVE - 1));
             if (jw >= npairs) continue;
             const u32 r0 = 2u * (first + (u32)u * THREADS + tid);
-            score_into(b.v[u].x, r0 >= r_lo && r0 < r_hi, idf);
-            score_into(b.v[u].y, r0 + 1u < r_hi, idf);           // r0 + 1 >= r_lo always holds
+            score_into(b.v[u].x, r0 >= r_lo && r0 < r_hi, idf, cls);
+            score_into(b.v[u].y, r0 + 1u < r_hi, idf, cls);      // r0 + 1 >= r_lo always holds
         }
     };
     // Only terms with postings in this tile get a phase (and its barrier): an empty phase still costs
@@ -695,16 +747,16 @@ __device__ __forceinline__ void sa_bm25_tile_item(const Bm25Params& p, const u32
         }
     };
     // one term phase: the first batch `cur`, then -- long slices -- the rest, `b` being the second batch (already requested)
-    auto run_phase = [&](const Batch& cur, Batch& b, u64 lo, u64 hi, u64 send, float idf) {
+    auto run_phase = [&](const Batch& cur, Batch& b, u64 lo, u64 hi, u64 send, float idf, u32 cls) {
         const u32 npairs = pairs_of(lo, hi);
-        score_batch(cur, lo, hi, 0, idf);
+        score_batch(cur, lo, hi, 0, idf, cls);
         if (npairs > (u32)PF * THREADS) {
             u32 first = (u32)PF * THREADS;
             while (first < npairs) {
                 const u32 nf = first + (u32)PF * THREADS;
                 Batch b2;
                 if (nf < npairs) b2 = load_batch(lo, hi, send, nf);
-                score_batch(b, lo, hi, first, idf);
+                score_batch(b, lo, hi, first, idf, cls);
                 if (nf < npairs) b = b2;
                 first = nf;
             }
@@ -714,6 +766,7 @@ __device__ __forceinline__ void sa_bm25_tile_item(const Bm25Params& p, const u32
     while (todo) {
         u64 L[4], H[4], S[4];
         float W[4];
+        u32 C[4] = {SA_OCC_SHOULD, SA_OCC_SHOULD, SA_OCC_SHOULD, SA_OCC_SHOULD};     // the phases' classes (MM == 2; else never read)
         sa_u64x2 P[4];
         {
             u32 g = todo;
@@ -726,6 +779,7 @@ __device__ __forceinline__ void sa_bm25_tile_item(const Bm25Params& p, const u32
                 H[i] = have ? lane64(r_hi, ti) : 0ull;
                 S[i] = (IMP && have) ? lane64(r_send, ti) : 0ull;
                 W[i] = __uint_as_float((u32)__builtin_amdgcn_readlane((int)__float_as_uint(r_idf), (int)ti));
+                if constexpr (OCC) C[i] = ((o_not >> ti) & 1u) ? SA_OCC_NOT : ((o_must >> ti) & 1u) ? SA_OCC_MUST : SA_OCC_SHOULD;
             }
         }
         // ---- phase 0 of the group
@@ -741,9 +795,9 @@ __device__ __forceinline__ void sa_bm25_tile_item(const Bm25Params& p, const u32
             if (!cleared) {                                     // first group: clear the accumulators behind the loads
 #pragma unroll
                 for (int j = 0; j < E; j++) acc[j * THREADS + tid] = 0.f;
-                if constexpr (MM) {                             // ... and the match counts, four docs per store
+                if constexpr (MM != 0) {                        // ... and the match states, a dword per store
 #pragma unroll
-                    for (int j = 0; j < E / 4; j++) ((u32*)mc)[j * THREADS + tid] = 0u;
+                    for (int j = 0; j < E * (int)sizeof(mc_t) / 4; j++) ((u32*)mc)[j * THREADS + tid] = 0u;
                 }
                 __syncthreads();
                 cleared = true;
@@ -751,7 +805,7 @@ __device__ __forceinline__ void sa_bm25_tile_item(const Bm25Params& p, const u32
             todo &= todo - 1u;
 #pragma unroll
             for (int u = 0; u < PF; u++) invalidate(cur.v[u], (u32)u * THREADS + tid, npairs);
-            run_phase(cur, b, lo, hi, S[0], W[0]);
+            run_phase(cur, b, lo, hi, S[0], W[0], C[0]);
             __syncthreads();
         }
         // ---- phases 1..3
@@ -770,7 +824,7 @@ __device__ __forceinline__ void sa_bm25_tile_item(const Bm25Params& p, const u32
                     if ((tid & ~(u32)(SA_WAVE - 1)) < npk[k]) {
                         sa_u64x2 v = P[k];
                         invalidate(v, tid, npk[k]);
-                        score_pair(v, W[k]);
+                        score_pair(v, W[k], C[k]);
                     }
                     __syncthreads();
                 }
@@ -786,6 +840,7 @@ __device__ __forceinline__ void sa_bm25_tile_item(const Bm25Params& p, const u32
             H[0] = H[1]; H[1] = H[2]; H[2] = H[3]; H[3] = 0;
             S[0] = S[1]; S[1] = S[2]; S[2] = S[3]; S[3] = 0;
             W[0] = W[1]; W[1] = W[2]; W[2] = W[3];
+            C[0] = C[1]; C[1] = C[2]; C[2] = C[3];
             P[0] = P[1]; P[1] = P[2]; P[2] = P[3];
             const u64 lo = L[0], hi = H[0];
             const u32 npairs = pairs_of(lo, hi);
@@ -794,7 +849,7 @@ __device__ __forceinline__ void sa_bm25_tile_item(const Bm25Params& p, const u32
             invalidate(cur.v[0], tid, npairs);
             load_rest(nxt, L[1], H[1], S[1]);                   // (the next group's first phase: nothing, L[1] = H[1] = 0)
             if (npairs > (u32)PF * THREADS) b = load_batch(lo, hi, S[0], (u32)PF * THREADS);   // requested before the first batch is scored
-            run_phase(cur, b, lo, hi, S[0], W[0]);
+            run_phase(cur, b, lo, hi, S[0], W[0], C[0]);
             __syncthreads();
         }
     }
@@ -808,12 +863,14 @@ __device__ __forceinline__ void sa_bm25_tile_item(const Bm25Params& p, const u32
     const u32 tile_n = remain < (u64)TILE ? (u32)remain : (u32)TILE;
     // minimum-should-match: a doc that matched fewer than mm slots leaves the ranking here, like a filtered one below (a tile without
     // a scored posting holds zeros only, and its counts were never cleared)
-    if constexpr (MM) {
-        if (cleared && mm > 1u) {                               // (uniform)
+    if constexpr (MM != 0) {
+        if (cleared && (OCC || mm > 1u)) {                      // (uniform; with occur classes m <= 1 is a test too)
 #pragma unroll
             for (int j = 0; j < E; j++) {
                 const u32 e = j * THREADS + tid;
-                if ((u32)mc[e] < mm) acc[e] = 0.f;
+                const u32 c = mc[e];
+                // (bits 6 and up: the required slots matched, and nothing above them -- no prohibited slot matched)
+                if (OCC ? ((c & (SA_OCC_MUST - 1u)) < mm || (c >> 6) != n_must) : (c < mm)) acc[e] = 0.f;
             }
             __syncthreads();
         }
@@ -970,17 +1027,18 @@ __device__ __forceinline__ void sa_bm25_tile_item(const Bm25Params& p, const u32
     }   // top-k
 }
 
-// MM (minimum-should-match): the match counts, a byte per accumulator and spare slot, lie BEHIND the item's LDS (the MODE 0 selection
+// MM (minimum-should-match; 2: with occur classes): the match states, one or two bytes per accumulator and spare slot, lie BEHIND the item's LDS (the MODE 0 selection
 // lists alias the accumulators, not the counts -- which are dead by then anyway)
-template <int TILE, int THREADS, int MODE, bool IMP, bool MM = false>
+template <int TILE, int THREADS, int MODE, bool IMP, int MM = 0>
 __global__ void __launch_bounds__(THREADS) sa_k_bm25_tiles(const Bm25Params p) {
     // grid (queries, tiles): x runs fastest, so the dispatch order is tile-major without a division
     constexpr size_t ITEM_U64 = sa_tile_smem_u64<TILE, MODE>();
-    __shared__ alignas(16) u64 smem[ITEM_U64 + (MM ? (TILE + SA_WAVE) / 8 : 0)];
+    typedef typename sa_match_state<MM>::type mc_t;
+    __shared__ alignas(16) u64 smem[ITEM_U64 + (MM ? (TILE + SA_WAVE) * sizeof(mc_t) / 8 : 0)];
     __shared__ float s_tab[sa_tile_tab_floats<THREADS, IMP>()];
     const u32 tile = p.tile0 + blockIdx.z * SA_GRID_Y + blockIdx.y;
     if (tile >= p.tile_end) return;
-    if constexpr (MM) sa_bm25_tile_item<TILE, THREADS, MODE, IMP, true>(p, tile, blockIdx.x, smem, s_tab, (unsigned char*)(smem + ITEM_U64));
+    if constexpr (MM != 0) sa_bm25_tile_item<TILE, THREADS, MODE, IMP, MM>(p, tile, blockIdx.x, smem, s_tab, (mc_t*)(smem + ITEM_U64));
     else sa_bm25_tile_item<TILE, THREADS, MODE, IMP>(p, tile, blockIdx.x, smem, s_tab);
 }
 
@@ -1820,10 +1878,14 @@ int sa_launch_make_bounds(sa_index* ix, const u32* d_terms, u32 BT, u32* d_bound
 
 #define SA_LAUNCH_TILE_MM(TILE, THREADS)                                                           \
     {                                                                                              \
-        if (MODE == 1 && p.imp)                                                                    \
-            hipLaunchKernelGGL((sa_k_bm25_tiles<TILE, THREADS, MODE, MODE == 1, true>), grid, dim3(THREADS), 0, st, p); \
+        if (MODE == 1 && p.imp && p.occur_off)                                                     \
+            hipLaunchKernelGGL((sa_k_bm25_tiles<TILE, THREADS, MODE, MODE == 1, 2>), grid, dim3(THREADS), 0, st, p); \
+        else if (p.occur_off)                                                                      \
+            hipLaunchKernelGGL((sa_k_bm25_tiles<TILE, THREADS, MODE, false, 2>), grid, dim3(THREADS), 0, st, p); \
+        else if (MODE == 1 && p.imp)                                                               \
+            hipLaunchKernelGGL((sa_k_bm25_tiles<TILE, THREADS, MODE, MODE == 1, 1>), grid, dim3(THREADS), 0, st, p); \
         else                                                                                       \
-            hipLaunchKernelGGL((sa_k_bm25_tiles<TILE, THREADS, MODE, false, true>), grid, dim3(THREADS), 0, st, p); \
+            hipLaunchKernelGGL((sa_k_bm25_tiles<TILE, THREADS, MODE, false, 1>), grid, dim3(THREADS), 0, st, p); \
     }                                                                                              \
     break
 
@@ -1841,14 +1903,14 @@ static int sa_launch_bm25_mode(sa_index* ix, const Bm25Params& p, hipStream_t st
     const u32 nt = p.tile_end - p.tile0;
     const u32 gy = nt < SA_GRID_Y ? nt : SA_GRID_Y;
     const dim3 grid(p.nq, gy, (nt + SA_GRID_Y - 1) / SA_GRID_Y);
-    if (p.min_match_off) {                                      // the counting instantiations (sa_min_match_tiles)
+    if (p.min_match_off) {                                      // the counting instantiations (sa_min_match_tiles; p.occur_off: those with occur classes)
         switch (ix->tile_docs) {
             case 1024: SA_LAUNCH_TILE_MM(1024, 128);
             case 2048: SA_LAUNCH_TILE_MM(2048, 64);
             case 4096: SA_LAUNCH_TILE_MM(4096, 128);
             case 8192: SA_LAUNCH_TILE_MM(8192, 256);
             default:
-                sa_set_error("minimum-should-match: no counting kernel for tile_docs %u", ix->tile_docs);
+                sa_set_error("minimum-should-match / occur: no counting kernel for tile_docs %u", ix->tile_docs);
                 return SA_ERR_UNSUPPORTED;
         }
         return SA_OK;

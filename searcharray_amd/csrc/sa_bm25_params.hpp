@@ -68,6 +68,10 @@ struct Bm25Params {
     u32* stats;            // diagnostics (sa_batch_stats): [B] candidates scored by the sparse path, or null
     const u32* qlist;      // queries to scan (after the sparse path took the others), or null: all B
     u32 nq;                // number of queries to scan (= B without a list)
+    // occur classes (sa_batch_set_occur), or 0: u32[B][2] per device row -- the masks of the query's required and prohibited slots --
+    // lie this many bytes behind `terms`, like the minimum-should-match values (min_match_off, which is then set as well and counts
+    // the remaining, optional slots).  Only the occur instantiations of sa_k_bm25_tiles read them
+    u32 occur_off;
     const u32* nq_dev;     // the same on the device (sa_k_bm25_tiles_list)
     // document filter of the batch (sa_filter.hpp), or null: every doc of the shard is eligible
     const u64* filt;       // one bit per local doc
@@ -81,7 +85,7 @@ struct Bm25Params {
     float* dense_out;      // [B][n_docs] or null
     u64* cand;             // [B][n_tiles][k] composite keys (global doc ids) or null
 };
-// (min_match_off sits in what was padding: the kernel arguments of every kernel stay where they were)
+// (min_match_off and occur_off sit in what was padding: the kernel arguments of every kernel stay where they were)
 static_assert(sizeof(Bm25Params) == 336, "Bm25Params: a new field moves the kernel arguments of every BM25 kernel");
 
 // host launchers of the BM25 kernels (sa_bm25.hip), called by the batch code (sa_batch.hip)
@@ -89,5 +93,5 @@ void sa_fill_params(const sa_index* ix, Bm25Params& p);
 u32 sa_tile_waves(u32 tile_docs);
 int sa_launch_bm25(sa_index* ix, const Bm25Params& p, hipStream_t st);                // per-query tile kernel (p.qlist: rows)
 int sa_launch_bm25_list(sa_index* ix, const Bm25Params& p, hipStream_t st);           // ... over the device's query list
-bool sa_min_match_tiles(u32 tile_docs);                                                // ... has counting instantiations (p.min_match_off) for this tile size
+bool sa_min_match_tiles(u32 tile_docs);                                                // ... has counting instantiations (p.min_match_off, p.occur_off) for this tile size
 int sa_launch_bm25_groups(sa_index* ix, const struct sa_batch* bt, const Bm25Params& p, u32 tile0, hipStream_t st);

@@ -377,6 +377,12 @@ extern "C" int sa_sharded_batch_set_min_match(sa_sharded_batch_t* bt, const uint
     return bt->sh->all([&](int g) { return sa_batch_set_min_match(bt->parts[(size_t)g], min_match); });
 }
 
+// (likewise: the classes are per query slot, the same on every shard)
+extern "C" int sa_sharded_batch_set_occur(sa_sharded_batch_t* bt, const uint8_t* occur) {
+    SA_ARG(bt && bt->sh, "null batch");
+    return bt->sh->all([&](int g) { return sa_batch_set_occur(bt->parts[(size_t)g], occur); });
+}
+
 extern "C" int sa_sharded_batch_destroy(sa_sharded_batch_t* bt) {
     if (!bt) return SA_OK;
     if (bt->sh) {

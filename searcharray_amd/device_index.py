@@ -389,16 +389,21 @@ class DeviceIndex(_options.OptionsMixin):
         return ms.value, ab.value
 
     def batch(self, queries: np.ndarray, k: int = 10, k1: float = 1.2, b: float = 0.75,
-              idf: Optional[np.ndarray] = None, opts=None, filter: Optional["DocFilter"] = None, min_match=None) -> "QueryBatch":
+              idf: Optional[np.ndarray] = None, opts=None, filter: Optional["DocFilter"] = None, min_match=None,
+              occur=None) -> "QueryBatch":
         """a resident top-k batch; ``filter``: a ``DocFilter`` of this index the batch ranks inside (``QueryBatch.set_filter``);
-        ``min_match``: per query, the number of query slots a doc must match (``QueryBatch.set_min_match``)"""
+        ``min_match``: per query, the number of query slots a doc must match (``QueryBatch.set_min_match``); ``occur``: per query
+        slot, 0 should / 1 must / 2 must_not (``QueryBatch.set_occur``)"""
         mm = None if min_match is None else min_match_values(min_match, np.asarray(queries).shape[0] if np.ndim(queries) == 2 else -1)
+        oc = None if occur is None else occur_values(occur, np.shape(queries) if np.ndim(queries) == 2 else None)
         bt = QueryBatch(self, queries, k=k, k1=k1, b=b, idf=idf, opts=opts)
         try:
             if filter is not None:
                 bt.set_filter(filter)
             if mm is not None:
                 bt.set_min_match(mm)
+            if oc is not None:
+                bt.set_occur(oc)
         except Exception:
             bt.close()
             raise
@@ -548,6 +553,19 @@ def min_match_values(values, n_queries: int) -> np.ndarray:
     return np.ascontiguousarray(np.minimum(a, 0xFFFFFFFF), dtype=np.uint32)
 
 
+def occur_values(values, shape) -> np.ndarray:
+    """occur classes of a batch, checked before anything is launched: an integer array [B][T] of 0 (should), 1 (must) and 2 (must_not)
+    -> uint8[B][T]; ``shape``: the batch's (B, T), or None: any 2-d shape"""
+    a = np.asarray(values)
+    if a.ndim != 2 or a.dtype.kind not in "iu":
+        raise ValueError("occur takes a 2-d integer array, one class per query slot")
+    if shape is not None and tuple(a.shape) != tuple(shape):
+        raise ValueError(f"occur needs one class per query slot {tuple(shape)}, got {tuple(a.shape)}")
+    if a.size and (int(a.min()) < 0 or int(a.max()) > 2):
+        raise ValueError("occur classes are 0 (should), 1 (must) and 2 (must_not)")
+    return np.ascontiguousarray(a, dtype=np.uint8)
+
+
 class QueryBatch(_options.OptionsMixin):
     _opt_setter = "sa_batch_set_options"
 
@@ -617,6 +635,20 @@ class QueryBatch(_options.OptionsMixin):
             return
         mm = min_match_values(values, self.B)
         self._call("sa_batch_set_min_match", self._h, p_u32(mm))
+
+    def set_occur(self, values):
+        """Occur classes (Lucene SHOULD / MUST / MUST_NOT): ``values[i][j]`` makes slot j of query i optional (0), required (1) or
+        prohibited (2); ``None`` clears them.  Query i keeps only the docs that match every required slot, no prohibited slot and at
+        least ``min_match[i]`` of the optional ones (``set_min_match``, which then counts optional slots only); every other doc scores
+        0, and a kept doc scores the sum of its non-prohibited slots, bit for bit.  Unknown terms never match: under must the query
+        returns nothing, under must_not they change nothing.  Applies from the next run on and persists across ``reset`` / ``step``
+        like ``set_min_match``; such a batch runs on the per-query tile kernels (``last_route()`` says 'exhaustive') and ``seeds()``
+        is all zero; all classes 0 leave the batch exactly as it was (``sa_batch_set_occur``)."""
+        if values is None:
+            self._call("sa_batch_set_occur", self._h, None)
+            return
+        oc = occur_values(values, (self.B, self.T))
+        self._call("sa_batch_set_occur", self._h, oc.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)))
 
     def run(self, sync: bool = True):
         self._call("sa_batch_run", self._h, 1 if sync else 0)

@@ -718,7 +718,7 @@ class SearchArray(ExtensionArray):
 
     # -- batched top-k (no counterpart in the reference: its callers loop over score() + argpartition)
     def search(self, queries, k: int = 10, similarity=default_bm25, devices=None, filter=None, mm=None,
-               q_op: str = "OR") -> Tuple[np.ndarray, np.ndarray]:
+               q_op: str = "OR", occur=None) -> Tuple[np.ndarray, np.ndarray]:
         """Top-``k`` docs for many queries at once, without materialising dense score vectors:
         ``queries`` is a list of token lists (each scored as a disjunction: the sum of its terms' BM25,
         ``np.sum([arr.score(t) for t in q], axis=0)`` in reference terms) or a list of strings (each run
@@ -737,8 +737,48 @@ class SearchArray(ExtensionArray):
         sequence with one such entry per query, each resolved against the number of the query's tokens (unknown tokens count as
         clauses, as in ``edismax``).  A row that matches fewer of the query's tokens scores 0; a token given twice counts twice.
         ``q_op="AND"`` requires all of them (``mm="100%"``, whatever ``mm`` says, as in ``edismax``).  Scores do not change, and
-        a ``filter`` applies as well."""
-        return self._topk(queries, k, similarity, phrases=False, devices=devices, filter=filter, mm=mm, q_op=q_op)
+        a ``filter`` applies as well.
+        ``occur``: Lucene's occur classes (``+tok`` / ``-tok``), per query.  Either one entry per query -- ``None`` or one symbol per
+        token of that query after tokenisation: ``"+"`` / ``"must"`` / 1, ``"-"`` / ``"must_not"`` / 2, ``""`` / ``"should"`` / 0 --
+        or ``occur="prefix"``: the classes are read from the queries themselves (``solr.split_occur``: a string query is split on
+        whitespace, a leading ``+`` / ``-`` of each clause is stripped and the rest tokenised; in a token list a leading ``+`` /
+        ``-`` of each token is stripped).  A row stays when it matches every must token, no must_not token and ``mm`` of the should
+        tokens -- ``mm`` and ``q_op`` then resolve against the number of SHOULD tokens.  A must_not token adds nothing to the score;
+        a query of must_not tokens only returns nothing; an unknown must token returns nothing for its query."""
+        return self._topk(queries, k, similarity, phrases=False, devices=devices, filter=filter, mm=mm, q_op=q_op, occur=occur)
+
+    def _occur_arg(self, queries, occur):
+        """``search(occur=)``, checked: (token lists, None or one list of classes 0 / 1 / 2 per query)"""
+        from .solr import occur_class, split_occur
+        if isinstance(occur, str):
+            if occur != "prefix":
+                raise ValueError("occur: 'prefix', or a sequence with one entry per query")
+            for q in queries:
+                if not isinstance(q, str):
+                    for t in q:
+                        self._check_token_arg(t)
+            split = [split_occur(q, self.tokenizer) for q in queries]
+            return [s[0] for s in split], [s[1] for s in split]
+        toks = [list(self.tokenizer(q)) if isinstance(q, str) else [self._check_token_arg(t) for t in q] for q in queries]
+        if occur is None:
+            return toks, None
+        if not is_list_like(occur):
+            raise ValueError("occur: 'prefix', or a sequence with one entry per query")
+        occur = list(occur)
+        if len(occur) != len(toks):
+            raise ValueError(f"occur needs one entry per query ({len(toks)}), got {len(occur)}")
+        classes = []
+        for i, (q, entry) in enumerate(zip(toks, occur)):
+            if entry is None:
+                classes.append([0] * len(q))
+                continue
+            if isinstance(entry, str) or not is_list_like(entry):
+                raise ValueError(f"occur entry {i}: None or a sequence with one symbol per token")
+            entry = list(entry)
+            if len(entry) != len(q):
+                raise ValueError(f"occur entry {i} needs one symbol per token ({len(q)}), got {len(entry)}")
+            classes.append([occur_class(sym) for sym in entry])
+        return toks, classes
 
     @staticmethod
     def _min_match_arg(mm, q_op, n_tokens):
@@ -804,19 +844,23 @@ class SearchArray(ExtensionArray):
         value or one per phrase).  Any phrase ``score`` takes is fine -- repeated tokens, long phrases, slop."""
         return self._topk(phrases, k, similarity, phrases=True, devices=devices, slop=slop)
 
-    def _topk(self, queries, k, similarity, phrases, devices=None, slop=0, filter=None, mm=None, q_op="OR"):
+    def _topk(self, queries, k, similarity, phrases, devices=None, slop=0, filter=None, mm=None, q_op="OR", occur=None):
         if getattr(similarity, "kind", None) != "bm25":
             raise ValueError("batched search needs a stock BM25 similarity (bm25_similarity(k1, b))")
         if self._rows is not None:
             raise ValueError("batched search runs on the whole indexed array, not on a slice")
-        toks = [list(self.tokenizer(q)) if isinstance(q, str) else [self._check_token_arg(t) for t in q] for q in queries]
+        toks, classes = self._occur_arg(queries, occur)
         B = len(toks)
         from .device_index import DocFilter
         from .sharded import ShardedDocFilter
         fmask = frows = None
         if filter is not None and not isinstance(filter, (DocFilter, ShardedDocFilter)):
             fmask, frows = self._filter_arg(filter)                 # (checked before anything is launched)
-        need = None if phrases else self._min_match_arg(mm, q_op, [len(q) for q in toks])
+        # (mm and q_op resolve against the query's should tokens: all of them without occur classes)
+        n_should = [len(q) if classes is None else sum(c == 0 for c in classes[i]) for i, q in enumerate(toks)]
+        need = None if phrases else self._min_match_arg(mm, q_op, n_should)
+        if classes is not None and not any(c for cl in classes for c in cl):
+            classes = None                                          # (all should: the batch as it always was)
         if B == 0 or len(self._core.doc_lens) == 0:
             return np.zeros((B, k), np.float32), np.full((B, k), NO_DOC, np.uint64)
         # (an explicit device list is honoured even when it names ONE device: a one-shard handle on that GPU)
@@ -833,8 +877,13 @@ class SearchArray(ExtensionArray):
             batch = dev.batch(mat, k=k, k1=similarity.k1, b=similarity.b)
         own = None
         try:
-            if need is not None and int(need.max()) > 1:
+            if need is not None and int(need.max()) > (1 if classes is None else 0):     # (beside a must token, m = 1 is a test too)
                 batch.set_min_match(need)
+            if classes is not None:
+                occ = np.zeros(mat.shape, dtype=np.uint8)
+                for i, cl in enumerate(classes):
+                    occ[i, :len(cl)] = cl
+                batch.set_occur(occ)
             if filter is not None:
                 sharded = devices is not None and len(devices) >= 1
                 if isinstance(filter, ShardedDocFilter) or (isinstance(filter, DocFilter) and not sharded):

@@ -24,7 +24,7 @@ import numpy as np
 from . import _lib
 from . import options as _options
 from . import roaringish as rz
-from .device_index import NO_TERM, DeviceIndex, compute_idf, min_match_values
+from .device_index import NO_TERM, DeviceIndex, compute_idf, min_match_values, occur_values
 
 
 def split_by_doc_range(words: np.ndarray, term_off: np.ndarray, bounds: Sequence[int]):
@@ -167,11 +167,12 @@ class ShardedIndex:
         return ShardedDocFilter(self, h)
 
     def batch(self, queries: np.ndarray, k: int = 10, k1: float = 1.2, b: float = 0.75, opts=None,
-              filter: Optional["ShardedDocFilter"] = None, min_match=None) -> "ShardedBatch":
+              filter: Optional["ShardedDocFilter"] = None, min_match=None, occur=None) -> "ShardedBatch":
         q = np.asarray(queries, dtype=np.int64)
         if q.ndim != 2:
             raise ValueError("queries must be [B][T] term ids")
         mm = None if min_match is None else min_match_values(min_match, q.shape[0])
+        oc = None if occur is None else occur_values(occur, q.shape)
         idf = _lib.as_f32(self.idfs(q.reshape(-1)).reshape(q.shape))
         terms = _lib.as_u32(np.where((q >= 0) & (q < self.n_terms), q, NO_TERM).astype(np.uint32))
         h = _lib.ctypes.c_void_p()
@@ -184,6 +185,8 @@ class ShardedIndex:
                 bt.set_filter(filter)
             if mm is not None:
                 bt.set_min_match(mm)
+            if oc is not None:
+                bt.set_occur(oc)
         except Exception:
             bt.close()
             raise
@@ -292,6 +295,16 @@ class ShardedBatch(_options.OptionsMixin):
             raise ValueError("phrase batches do not take minimum-should-match")
         mm = min_match_values(values, self.B)
         self._call("sa_sharded_batch_set_min_match", self._h, _lib.p_u32(mm))
+
+    def set_occur(self, values):
+        """occur classes, the same per-slot classes on every shard's batch (``QueryBatch.set_occur``); ``None`` clears them"""
+        if values is None:
+            self._call("sa_sharded_batch_set_occur", self._h, None)
+            return
+        if self.T is None:
+            raise ValueError("phrase batches do not take occur classes")
+        oc = occur_values(values, (self.B, self.T))
+        self._call("sa_sharded_batch_set_occur", self._h, oc.ctypes.data_as(_lib.ctypes.POINTER(_lib.ctypes.c_uint8)))
 
     def run(self, sync: bool = True):
         self._call("sa_sharded_batch_run", self._h, 1 if sync else 0)

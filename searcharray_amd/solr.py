@@ -75,6 +75,51 @@ def parse_min_should_match(num_clauses: int, spec: str) -> int:
     return required
 
 
+OCCUR_SHOULD, OCCUR_MUST, OCCUR_MUST_NOT = 0, 1, 2
+_OCCUR_SYMBOLS = {"": OCCUR_SHOULD, "should": OCCUR_SHOULD, "+": OCCUR_MUST, "must": OCCUR_MUST, "-": OCCUR_MUST_NOT,
+                  "must_not": OCCUR_MUST_NOT}
+
+
+def occur_class(symbol) -> int:
+    """one occur symbol of ``SearchArray.search(occur=...)`` -> 0 (should), 1 (must), 2 (must_not): ``""`` / ``"should"`` / 0,
+    ``"+"`` / ``"must"`` / 1, ``"-"`` / ``"must_not"`` / 2"""
+    if isinstance(symbol, str):
+        if symbol in _OCCUR_SYMBOLS:
+            return _OCCUR_SYMBOLS[symbol]
+    elif not isinstance(symbol, bool) and isinstance(symbol, (int, np.integer)) and 0 <= int(symbol) <= 2:
+        return int(symbol)
+    raise ValueError(f"occur symbols are '+' / 'must' / 1, '-' / 'must_not' / 2 and '' / 'should' / 0, got {symbol!r}")
+
+
+def split_occur(query_or_tokens, tokenizer) -> Tuple[List[str], List[int]]:
+    """The ``+tok`` / ``-tok`` prefixes of a Lucene / Solr query, read once: ``(tokens, classes)`` with one class (0 should, 1 must,
+    2 must_not) per token, ready for ``SearchArray.search(tokens_per_query, occur=classes_per_query)``.
+    A string is split on whitespace into clauses; one leading ``+`` / ``-`` of a clause is stripped and the rest is run through
+    ``tokenizer`` -- every token a clause yields inherits the clause's class.  In a token list one leading ``+`` / ``-`` of each token
+    is stripped (``tokenizer`` is not applied).  A clause or token that is nothing but the sign is left as it is."""
+    def sign(text):
+        if len(text) > 1 and text[0] in "+-":
+            return text[1:], OCCUR_MUST if text[0] == "+" else OCCUR_MUST_NOT
+        return text, OCCUR_SHOULD
+
+    tokens: List[str] = []
+    classes: List[int] = []
+    if isinstance(query_or_tokens, str):
+        for clause in query_or_tokens.split():
+            rest, cls = sign(clause)
+            for tok in tokenizer(rest):
+                tokens.append(tok)
+                classes.append(cls)
+    else:
+        for tok in query_or_tokens:
+            if not isinstance(tok, str):
+                raise TypeError("Expected a string")
+            rest, cls = sign(tok)
+            tokens.append(rest)
+            classes.append(cls)
+    return tokens, classes
+
+
 def parse_field_boosts(field_lists: Optional[Sequence[str]]) -> Dict[str, Optional[float]]:
     """``["title^10", "body"]`` -> ``{"title": 10.0, "body": None}`` (qf, pf, pf2, pf3)."""
     boosts: Dict[str, Optional[float]] = {}

@@ -411,9 +411,17 @@ int sa_filter_destroy(sa_filter_t* filter);
  * whose results have not been fetched keeps the filter it ran with.  The filter persists across sa_batch_reset / sa_batch_step like the
  * batch's options.  Routes: the staged-tile route, the grouped overlay and the per-query tile kernels honour the filter; dynamic
  * pruning does not, and the route rule never picks it for a filtered batch (option sparse = 1 with a filter: the exhaustive kernels,
- * sa_batch_last_route says 0).  A filter of another index -> SA_ERR_ARG.  Phrase batches and the timing option no_topk do not take
- * a filter (SA_ERR_UNSUPPORTED). */
+ * sa_batch_last_route says 0).  A filter of another index -> SA_ERR_ARG.  Phrase batches (they have sa_phrase_batch_set_filter, as
+ * they have sa_phrase_batch_reset) and the timing option no_topk do not take a filter here (SA_ERR_UNSUPPORTED). */
 int sa_batch_set_filter(sa_batch_t* batch, sa_filter_t* filter);
+/* The same for a PHRASE batch: from its next run on, phrase i returns exactly the top-k of its unfiltered scores (any phrase the batch
+ * takes: exact, repeated terms, more than 18 terms, slop > 0) with the scores of the non-eligible documents set to 0 -- bit for bit,
+ * idf, average doc length and corpus size those of the whole index.  The filter is applied inside every ranking kernel, before any
+ * selection; excluded documents are not aligned at all, tiles and blocks without an eligible document are left at once.  NULL clears.
+ * Nothing is prepared again (a phrase batch has no state that depends on the filter); the filter persists across
+ * sa_phrase_batch_reset; replacing or clearing a held filter waits for the batch's stream first.  A filter of another index, or a BM25
+ * batch -> SA_ERR_ARG. */
+int sa_phrase_batch_set_filter(sa_batch_t* batch, sa_filter_t* filter);
 /* MINIMUM-SHOULD-MATCH (Solr `mm`, `q.op=AND`) for BM25 batches.  min_match: n_queries values in CALLER query order (NULL clears them).
  * With value m, query i keeps only the documents that match at least m of its query SLOTS; every other document scores 0, as under a
  * filter.  A slot matches a document when its own contribution fl(factor x weight) is > 0; slots count separately (a term given twice
@@ -620,6 +628,8 @@ int sa_sharded_filter_count(sa_sharded_filter_t* filter, uint64_t* n_out);
 int sa_sharded_filter_destroy(sa_sharded_filter_t* filter);
 /* sa_batch_set_filter on every shard's batch (NULL clears) */
 int sa_sharded_batch_set_filter(sa_sharded_batch_t* batch, sa_sharded_filter_t* filter);
+/* sa_phrase_batch_set_filter on every shard's phrase batch (NULL clears) */
+int sa_sharded_phrase_batch_set_filter(sa_sharded_batch_t* batch, sa_sharded_filter_t* filter);
 /* sa_batch_set_min_match with the same n_queries values on every shard's batch (NULL clears): the count is per document and shards are
  * doc ranges */
 int sa_sharded_batch_set_min_match(sa_sharded_batch_t* batch, const uint32_t* min_match);

@@ -150,11 +150,13 @@ PROTOTYPES = {
     "sa_filter_fetch": (c_int, [c_void_p, c_void_p]),
     "sa_filter_destroy": (c_int, [c_void_p]),
     "sa_batch_set_filter": (c_int, [c_void_p, c_void_p]),
+    "sa_phrase_batch_set_filter": (c_int, [c_void_p, c_void_p]),
     "sa_sharded_filter_create_from_rows": (c_int, [c_void_p, u64p, c_uint64, POINTER(c_void_p)]),
     "sa_sharded_filter_create_from_mask": (c_int, [c_void_p, c_void_p, c_uint64, POINTER(c_void_p)]),
     "sa_sharded_filter_count": (c_int, [c_void_p, u64p]),
     "sa_sharded_filter_destroy": (c_int, [c_void_p]),
     "sa_sharded_batch_set_filter": (c_int, [c_void_p, c_void_p]),
+    "sa_sharded_phrase_batch_set_filter": (c_int, [c_void_p, c_void_p]),
     "sa_batch_set_min_match": (c_int, [c_void_p, u32p]),
     "sa_batch_row_order": (c_int, [c_void_p, u32p]),
     "sa_sharded_batch_set_min_match": (c_int, [c_void_p, u32p]),

@@ -54,6 +54,7 @@ struct sa_batch {
     std::vector<float> step_idf;    // sa_batch_step: the query set's weights, gathered from the index's idf table
     // the document filter the batch ranks inside (sa_batch_set_filter), or null.  Setting one prepares the loaded query set again (from
     // the upload image it was filled into): starting bounds, groups and the staged plan depend on the filter
+    // (a phrase batch holds its filter here too -- sa_phrase_batch_set_filter --, and has nothing to prepare again)
     std::shared_ptr<sa_filter_data> filter;
     // minimum-should-match (sa_batch_set_min_match): per CALLER query, the number of query slots a doc must match; empty: none set.
     // Every fill writes the values in device-row order into the upload block (d_min_match).  mm_on: some value is > 1 -- the batch

@@ -1,7 +1,8 @@
 // sa_filter.hpp -- a document filter of one index (Part 2b of the C ABI, sa_filter.hip): an immutable bitmap over the shard-local
-// documents that a BM25 batch ranks inside (sa_batch_set_filter).  Bit doc & 63 of word doc >> 6 (the same bytes read as u32
+// documents that a BM25 batch (sa_batch_set_filter) or a phrase batch (sa_phrase_batch_set_filter) ranks inside.  Bit doc & 63 of word doc >> 6 (the same bytes read as u32
 // words: bit doc & 31 of word doc >> 5); the bits from n_docs on are always 0, and the allocation runs one whole block past the
-// last one, all zeros, so that a kernel may read the words of a whole tile wherever the tile starts.  blk[i] = eligible documents
+// last one, all zeros, so that a kernel may read the words of a whole tile of up to 1024 docs wherever the tile starts (kernels with
+// larger tiles bound their reads by n_words).  blk[i] = eligible documents
 // among [i * SA_FILTER_BLOCK, (i + 1) * SA_FILTER_BLOCK): every scoring tile size is a multiple of the block, so a tile kernel
 // knows from its blocks' counts that a tile holds nothing without reading the words.
 #pragma once

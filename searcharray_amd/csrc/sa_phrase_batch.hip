@@ -56,7 +56,25 @@ struct PhraseTileParams {
     const u32* docdir;     // index doc directory [n_dd_terms][n_docs]
     const u32* dd_slot;    // [n_terms]
     int use_docdir;        // 0: binary-search every probe (SA_PHRASE_DOCDIR=0, tests)
+    // the batch's document filter (sa_filter.hpp; the FILT instantiations): bit doc & 63 of word doc >> 6, eligible docs per 1024-doc block
+    const u64* filt;
+    const u32* filt_blk;
+    u32 filt_nblk;
+    u64 filt_nwords;
 };
+
+// the ranking kernels' view of the batch's document filter (all null / 0: none)
+struct PhraseFilt { const u64* words; const u32* blk; u32 n_blk; };
+
+// (uniform) no eligible doc among the filter blocks of tile `tile` -- blocks past the shard's last one count as empty
+template <int TILE>
+__device__ __forceinline__ bool sa_filter_tile_empty(const u32* __restrict__ blk, const u32 n_blk, const u32 tile) {
+    constexpr u32 NB = (u32)TILE / SA_FILTER_BLOCK;
+    u32 any = 0;
+#pragma unroll
+    for (u32 i = 0; i < NB; i++) { const u32 bi = tile * NB + i; any |= bi < n_blk ? blk[bi] : 0u; }
+    return any == 0u;
+}
 
 // first word of each phrase term at or after every tile boundary, relative to the term's base
 __global__ void __launch_bounds__(256)
@@ -79,7 +97,11 @@ sa_k_make_word_bounds(const u64* __restrict__ words, const u64* __restrict__ ter
     }
 }
 
-template <int TILE, int THREADS>
+// FILT: the batch has a document filter.  A phrase is an AND, so an excluded doc needs no alignment at all: a tile without an
+// eligible doc is left before any slice is touched, the tile's filter words are staged in LDS and an anchor word of an excluded
+// doc is dropped before its probes (both parts of a middle-out plan skip it: min(0, 0) = 0) -- the doc's count stays 0, it scores
+// 0 and the selection never sees it.  The unfiltered instantiations contain none of it.
+template <int TILE, int THREADS, bool FILT>
 __global__ void __launch_bounds__(THREADS) sa_k_phrase_tiles(const PhraseTileParams p) {
     constexpr int E = TILE / THREADS;
     __shared__ u32 cnt_a[TILE];                      // match counts, later the fp32 scores
@@ -95,6 +117,14 @@ __global__ void __launch_bounds__(THREADS) sa_k_phrase_tiles(const PhraseTilePar
     const u32* plan = p.plan + (u64)q * 4;
     const u32 Tq = plan[0], split = plan[1];
     if (Tq == 0) return;                             // a term is unknown: zeros (postings.py:705-708)
+    u64* s_filt = nullptr;                           // the tile's filter words (FILT)
+    if constexpr (FILT) {
+        if (sa_filter_tile_empty<TILE>(p.filt_blk, p.filt_nblk, tile)) return;      // uniform
+        __shared__ u64 s_filt_words[TILE / 64];
+        s_filt = s_filt_words;
+        // (the last tile may reach past the filter's allocation: words behind the shard's last one are empty)
+        if (tid < (u32)TILE / 64u) { const u64 wi = (tile_base >> 6) + tid; s_filt[tid] = wi < p.filt_nwords ? p.filt[wi] : 0ull; }
+    }
     u32 slot_val = 0xFFFFFFFFu;
     if ((tid & (SA_WAVE - 1)) < 32u)
         slot_val = __hip_atomic_load(&p.slots[q * 32u + (tid & 31u)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -133,6 +163,10 @@ __global__ void __launch_bounds__(THREADS) sa_k_phrase_tiles(const PhraseTilePar
         const u32 na = (u32)(s_hi[t0 + anchor] - alo);
         for (u32 i = tid; i < na; i += THREADS) {
             const u64 w = p.words[alo + i];
+            if constexpr (FILT) {                    // an excluded doc: one LDS read, no probes
+                const u32 e = (u32)((w >> SA_KEY_SHIFT) - tile_base);
+                if (!((s_filt[e >> 6] >> (e & 63u)) & 1ull)) continue;
+            }
             const u64 m = sa_phrase_anchor_mask_win(w, t1 - t0, anchor, [&](int t, u64 h, bool want_prev, bool want_next) -> u64 {
                 const u32 dd = s_dd[t0 + t];
                 if (dd != SA_DD_NONE)                // uniform per term
@@ -180,14 +214,16 @@ __global__ void __launch_bounds__(THREADS) sa_k_phrase_tiles(const PhraseTilePar
 // into BM25 scores (reference bm25.pyx:11-25, the op order of sa_k_bm25_from_tf -- fused here: one launch less per
 // phrase, and a batch of short phrases is bound by the host's launch rate) and runs the same pruned selection as
 // the phrase tiles
+// (filt.words != null, uniform: a tile without an eligible doc is left at once, and an excluded doc scores 0 -- its count is not even read)
 template <int TILE, int THREADS>
 __global__ void __launch_bounds__(THREADS)
 sa_k_dense_topk_tiles(const float* __restrict__ counts, const float* __restrict__ dl, float avgdl, float idf, float k1, float b,
                       u64 n_docs, u64 doc_base, u32 q, u32 k, u32* __restrict__ slots,
-                      u64* __restrict__ cand, u32 cand_cap, u32* __restrict__ cand_cnt) {
+                      u64* __restrict__ cand, u32 cand_cap, u32* __restrict__ cand_cnt, const PhraseFilt filt) {
     constexpr int E = TILE / THREADS;
     __shared__ float acc[TILE];
     const u32 tid = threadIdx.x, tile = blockIdx.x;
+    if (filt.words && sa_filter_tile_empty<TILE>(filt.blk, filt.n_blk, tile)) return;
     const u64 tile_base = (u64)tile * TILE;
     const float one_minus_b = 1.0f - b;
     u32 slot_val = 0xFFFFFFFFu;
@@ -197,7 +233,7 @@ sa_k_dense_topk_tiles(const float* __restrict__ counts, const float* __restrict_
     for (int j = 0; j < E; j++) {                    // (a thread loads exactly the elements it owns in the selection)
         const u64 d = tile_base + (u64)(j * THREADS) + tid;
         float sc = 0.f;
-        if (d < n_docs) {
+        if (d < n_docs && (!filt.words || ((filt.words[d >> 6] >> (d & 63u)) & 1ull))) {
             const float t = counts[d];
             if (t != 0.f) {                                      // (0 / (0 + norm) * idf = 0: docs without a match are not ranked)
                 const float norm = __fmul_rn(k1, __fadd_rn(one_minus_b, __fmul_rn(b, __fdiv_rn(dl[d], avgdl))));
@@ -209,12 +245,14 @@ sa_k_dense_topk_tiles(const float* __restrict__ counts, const float* __restrict_
     sa_tile_topk_pruned<TILE, THREADS>(acc, slot_val, q, tile, doc_base + tile_base, k, slots, cand, cand_cap, cand_cnt);
 }
 
-// the same for several dense-route phrases in ONE launch: blockIdx.y picks the phrase (its counts, idf and batch row)
+// the same for several dense-route phrases in ONE launch: blockIdx.y picks the phrase (its counts, idf and batch row).
+// Under a filter this launch still puts the count vectors back to zeros -- excluded docs and tiles without an eligible doc
+// included: only the score is suppressed (an empty tile is zeroed and left before the selection).
 template <int TILE, int THREADS>
 __global__ void __launch_bounds__(THREADS)
 sa_k_dense_topk_tiles_multi(const sa_dense_rank_job* __restrict__ jobs, const float* __restrict__ dl, float avgdl, float k1, float b,
                             u64 n_docs, u64 doc_base, u32 k, u32* __restrict__ slots, u64* __restrict__ cand, u32 cand_cap,
-                            u32* __restrict__ cand_cnt) {
+                            u32* __restrict__ cand_cnt, const PhraseFilt filt) {
     constexpr int E = TILE / THREADS;
     __shared__ float acc[TILE];
     const sa_dense_rank_job J = jobs[blockIdx.y];
@@ -224,6 +262,14 @@ sa_k_dense_topk_tiles_multi(const sa_dense_rank_job* __restrict__ jobs, const fl
     if (tid == 0) J.touched[tile] = 0;
     const u64 tile_base = (u64)tile * TILE;
     const float one_minus_b = 1.0f - b;
+    if (filt.words && sa_filter_tile_empty<TILE>(filt.blk, filt.n_blk, tile)) {      // (uniform) nothing to rank: the counts are put back, no more
+#pragma unroll
+        for (int j = 0; j < E; j++) {
+            const u64 d = tile_base + (u64)(j * THREADS) + tid;
+            if (d < n_docs && J.counts[d] != 0.f) ((float*)J.counts)[d] = 0.f;
+        }
+        return;
+    }
     u32 slot_val = 0xFFFFFFFFu;
     if ((tid & (SA_WAVE - 1)) < 32u)
         slot_val = __hip_atomic_load(&slots[q * 32u + (tid & 31u)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -235,8 +281,10 @@ sa_k_dense_topk_tiles_multi(const sa_dense_rank_job* __restrict__ jobs, const fl
             const float t = J.counts[d];
             if (t != 0.f) {
                 ((float*)J.counts)[d] = 0.f;                     // the count vectors of this route are all zeros between runs (sa_span_counts_batch)
-                const float norm = __fmul_rn(k1, __fadd_rn(one_minus_b, __fmul_rn(b, __fdiv_rn(dl[d], avgdl))));
-                sc = __fmul_rn(__fdiv_rn(t, __fadd_rn(t, norm)), J.idf);
+                if (!filt.words || ((filt.words[d >> 6] >> (d & 63u)) & 1ull)) {      // (an excluded doc: zeroed like the others, not scored)
+                    const float norm = __fmul_rn(k1, __fadd_rn(one_minus_b, __fmul_rn(b, __fdiv_rn(dl[d], avgdl))));
+                    sc = __fmul_rn(__fdiv_rn(t, __fadd_rn(t, norm)), J.idf);
+                }
             }
         }
         acc[j * THREADS + tid] = sc;
@@ -260,12 +308,26 @@ int sa_launch_phrase_tiles(sa_batch* bt, hipStream_t st) {
     p.terms = bt->d_terms; p.wlen = bt->d_wlen; p.docdir = ix->d_docdir; p.dd_slot = ix->d_dd_slot;
     p.use_docdir = ix->n_dd_terms > 0 ? 1 : 0;
     if (sa_opt(bt->opts.phrase_docdir, 1) == 0) p.use_docdir = 0;
+    // the batch's document filter (sa_phrase_batch_set_filter): every ranking site below clears the excluded docs before the pruned
+    // selection sees a score -- its bound slots assume that any doc it is shown may be a result
+    const sa_filter_data* fd = bt->filter.get();
+    PhraseFilt pf = {nullptr, nullptr, 0u};
+    if (fd) {
+        pf.words = fd->d_words; pf.blk = fd->d_blk; pf.n_blk = fd->n_blocks;
+        p.filt = fd->d_words; p.filt_blk = fd->d_blk; p.filt_nblk = fd->n_blocks; p.filt_nwords = fd->n_words;
+    }
+    const bool trace = sa_opt(bt->opts.trace, 0) != 0;
+    u32 n_fused = 0, n_shared = 0, n_single = 0;     // dense-route phrases by ranking site (trace)
     const u64 n_items = (u64)bt->B * bt->pn_tiles;
     if (bt->dense_rows.size() < bt->B) {             // (rows on the dense route have plan[0] == 0: their items leave at once)
-        if (bt->ptile == 2048)
-            hipLaunchKernelGGL((sa_k_phrase_tiles<2048, SA_PTHREADS>), dim3((u32)n_items), dim3(SA_PTHREADS), 0, st, p);
-        else
-            hipLaunchKernelGGL((sa_k_phrase_tiles<4096, SA_PTHREADS>), dim3((u32)n_items), dim3(SA_PTHREADS), 0, st, p);
+        const dim3 grid((u32)n_items), block(SA_PTHREADS);
+        if (bt->ptile == 2048) {
+            if (fd) hipLaunchKernelGGL((sa_k_phrase_tiles<2048, SA_PTHREADS, true>), grid, block, 0, st, p);
+            else hipLaunchKernelGGL((sa_k_phrase_tiles<2048, SA_PTHREADS, false>), grid, block, 0, st, p);
+        } else {
+            if (fd) hipLaunchKernelGGL((sa_k_phrase_tiles<4096, SA_PTHREADS, true>), grid, block, 0, st, p);
+            else hipLaunchKernelGGL((sa_k_phrase_tiles<4096, SA_PTHREADS, false>), grid, block, 0, st, p);
+        }
     }
     // the dense route: counts of the whole shard by the single-phrase kernels (general bigram chain with the
     // same-term rule / span machine for slop > 0), BM25 in place, then the ranking kernel above
@@ -322,18 +384,20 @@ int sa_launch_phrase_tiles(sa_batch* bt, hipStream_t st) {
             SpanRankCtx rc;
             rc.doc_lens = ix->d_doc_lens; rc.avgdl = ix->avg_doc_len; rc.k1 = bt->k1; rc.b = bt->b; rc.k = bt->k;
             rc.slots = bt->d_slots; rc.cand = bt->d_cand; rc.cand_cap = bt->cand_cap; rc.cand_cnt = bt->d_cand_cnt; rc.doc_base = ix->doc_base;
+            rc.filt = pf.words; rc.filt_blk = pf.blk;
             SA_TRY(sa_span_counts_batch(ix, st, (int)rows.size(), tp.data(), tn.data(), ts.data(), idfs.data(), rows.data(), outs.data(),
                                         handled.data(), &d_rj, &n_rj, bt->ptile == 2048 ? 11u : 12u, &rc));
-            for (size_t i = 0; i < rows.size(); i++) if (handled[i]) taken[rows[i]] = 1;
+            for (size_t i = 0; i < rows.size(); i++) if (handled[i]) { taken[rows[i]] = 1; n_fused++; }
+            n_shared = (u32)n_rj; n_fused -= n_shared;             // (a phrase taken without a ranking job ranked inside the span kernel)
             if (n_rj > 0) {
                 if (bt->ptile == 2048)
                     hipLaunchKernelGGL((sa_k_dense_topk_tiles_multi<2048, SA_PTHREADS>), dim3(bt->pn_tiles, (u32)n_rj), dim3(SA_PTHREADS), 0, st,
                                        d_rj, (const float*)ix->d_doc_lens, ix->avg_doc_len, bt->k1, bt->b, ix->n_docs,
-                                       ix->doc_base, bt->k, bt->d_slots, bt->d_cand, bt->cand_cap, bt->d_cand_cnt);
+                                       ix->doc_base, bt->k, bt->d_slots, bt->d_cand, bt->cand_cap, bt->d_cand_cnt, pf);
                 else
                     hipLaunchKernelGGL((sa_k_dense_topk_tiles_multi<4096, SA_PTHREADS>), dim3(bt->pn_tiles, (u32)n_rj), dim3(SA_PTHREADS), 0, st,
                                        d_rj, (const float*)ix->d_doc_lens, ix->avg_doc_len, bt->k1, bt->b, ix->n_docs,
-                                       ix->doc_base, bt->k, bt->d_slots, bt->d_cand, bt->cand_cap, bt->d_cand_cnt);
+                                       ix->doc_base, bt->k, bt->d_slots, bt->d_cand, bt->cand_cap, bt->d_cand_cnt, pf);
                 ix->span_counts_dirty = false;
             }
         }
@@ -344,21 +408,25 @@ int sa_launch_phrase_tiles(sa_batch* bt, hipStream_t st) {
         const int j = (int)(nth++ % (u32)n_lanes) - 1;
         const hipStream_t ls = j < 0 ? st : ix->lane_stream[j];
         Lane lane(ix, j);
+        n_single++;
         float* d_scores = nullptr;
         SA_TRY(sa_phrase_dense_counts_device(ix, &bt->h_pterms[(size_t)row * bt->T], bt->h_pn[row], bt->h_pslop[row], &d_scores));
         if (bt->ptile == 2048)
             hipLaunchKernelGGL((sa_k_dense_topk_tiles<2048, SA_PTHREADS>), dim3(bt->pn_tiles), dim3(SA_PTHREADS), 0, ls, (const float*)d_scores,
                                (const float*)ix->d_doc_lens, ix->avg_doc_len, bt->h_pidf[row], bt->k1, bt->b,
-                               ix->n_docs, ix->doc_base, row, bt->k, bt->d_slots, bt->d_cand, bt->cand_cap, bt->d_cand_cnt);
+                               ix->n_docs, ix->doc_base, row, bt->k, bt->d_slots, bt->d_cand, bt->cand_cap, bt->d_cand_cnt, pf);
         else
             hipLaunchKernelGGL((sa_k_dense_topk_tiles<4096, SA_PTHREADS>), dim3(bt->pn_tiles), dim3(SA_PTHREADS), 0, ls, (const float*)d_scores,
                                (const float*)ix->d_doc_lens, ix->avg_doc_len, bt->h_pidf[row], bt->k1, bt->b,
-                               ix->n_docs, ix->doc_base, row, bt->k, bt->d_slots, bt->d_cand, bt->cand_cap, bt->d_cand_cnt);
+                               ix->n_docs, ix->doc_base, row, bt->k, bt->d_slots, bt->d_cand, bt->cand_cap, bt->d_cand_cnt, pf);
     }
     for (int j = 0; j + 1 < n_lanes; j++) {                    // the merge waits for every lane
         SA_HIP(hipEventRecord(bt->ev_side[1], ix->lane_stream[j]));
         SA_HIP(hipStreamWaitEvent(st, bt->ev_side[1], 0));
     }
+    if (trace)
+        fprintf(stderr, "sa_phrase_batch: ranked %u phrases by the tile kernel, %u inside the span kernel, %u by the shared ranking launch, %u one by one%s\n",
+                bt->B - (u32)bt->dense_rows.size(), n_fused, n_shared, n_single, fd ? " (filtered)" : "");
     return SA_OK;
 }
 
@@ -531,4 +599,23 @@ extern "C" int sa_phrase_batch_reset(sa_batch_t* bt, const uint32_t* terms, cons
     std::lock_guard<std::mutex> g(ix->mu);
     SA_HIP(hipSetDevice(ix->device));
     return sa_phrase_batch_fill(bt, terms, n_terms, slop, idf);
+}
+
+// Part 2b for phrase batches: the batch ranks inside `f` from its next run on (null: the whole index), across sa_phrase_batch_reset
+// too.  Nothing is prepared again -- a phrase batch has no starting bounds, groups or plan that depend on the filter, and every run
+// clears its slots and candidate counts.  (sa_batch_set_filter keeps refusing a phrase handle, as sa_batch_reset does.)
+extern "C" int sa_phrase_batch_set_filter(sa_batch_t* bt, sa_filter_t* f) {
+    SA_ARG(bt && bt->ix, "null batch");
+    if (bt->kind != 1) { sa_set_error("sa_phrase_batch_set_filter takes a phrase batch (BM25 batches: sa_batch_set_filter)"); return SA_ERR_ARG; }
+    SA_ARG(!f || f->d, "null filter");
+    sa_index* ix = bt->ix;
+    SA_ARG(!f || (f->d->ix == ix && f->d->n_docs == ix->n_docs), "the filter was built for another index");
+    std::lock_guard<std::mutex> g(ix->mu);
+    SA_HIP(hipSetDevice(ix->device));
+    if (!f && !bt->filter) return SA_OK;
+    // (runs in flight read the bitmap this call may release; the dense-route lanes have joined the batch's stream by event)
+    if (bt->filter) SA_HIP(hipStreamSynchronize(bt->st));
+    bt->filter = f ? f->d : nullptr;
+    if (sa_opt(bt->opts.trace, 0)) fprintf(stderr, "sa_phrase_batch_set_filter: %llu of %llu docs eligible\n", f ? (unsigned long long)f->d->count : (unsigned long long)ix->n_docs, (unsigned long long)ix->n_docs);
+    return SA_OK;
 }

@@ -371,6 +371,13 @@ extern "C" int sa_sharded_batch_set_filter(sa_sharded_batch_t* bt, sa_sharded_fi
     return bt->sh->all([&](int g) { return sa_batch_set_filter(bt->parts[(size_t)g], f ? f->parts[(size_t)g] : nullptr); });
 }
 
+// (the same for the shards' phrase batches)
+extern "C" int sa_sharded_phrase_batch_set_filter(sa_sharded_batch_t* bt, sa_sharded_filter_t* f) {
+    SA_ARG(bt && bt->sh, "null batch");
+    SA_ARG(!f || (f->sh == bt->sh && f->parts.size() == bt->parts.size()), "the filter belongs to another sharded index");
+    return bt->sh->all([&](int g) { return sa_phrase_batch_set_filter(bt->parts[(size_t)g], f ? f->parts[(size_t)g] : nullptr); });
+}
+
 // (collective like set_filter; every shard's batch gets the same per-query values)
 extern "C" int sa_sharded_batch_set_min_match(sa_sharded_batch_t* bt, const uint32_t* min_match) {
     SA_ARG(bt && bt->sh, "null batch");

@@ -36,6 +36,7 @@
 #include "sa_index.hpp"
 #include "sa_topk.hpp"
 #include "sa_scan.hpp"
+#include "sa_filter.hpp"
 #include "../../include/searcharray_hip.h"
 #include <stdlib.h>
 #include <algorithm>
@@ -1614,8 +1615,15 @@ extern "C" int sa_debug_span_probe_read(unsigned long long* out8, int clear) {
 #define SA_SPP(i) do { } while (0)
 #endif
 
-template <int TT, int NTAB_>
+// FILT (ranked mode of a filtered phrase batch only: p.rank.filt / filt_blk are set): a doc's filter bit is part of its slot's
+// `valid`, so an excluded doc is never gathered, never compacted in, never run through a machine, and its slot scores 0; a block of
+// 512 docs (doc mode) whose 1024-doc filter block holds no eligible doc leaves at once.  The other instantiations contain none of it.
+template <int TT, int NTAB_, bool FILT = false>
 __device__ __forceinline__ void sa_span_doc_fused_body(const SpanDocParams& p, const u32 block) {
+    if constexpr (FILT) {
+        // (anchor mode: a slot is a word of the anchor's list, not a doc -- no block to skip, only the per-doc bit below)
+        if (p.anchor < 0 && sa_glob(p.rank.filt_blk)[((u64)block * SA_SPAN_FD) / SA_FILTER_BLOCK] == 0u) return;     // uniform
+    }
 #ifdef SA_PROBE
     u64 sp_last = __builtin_amdgcn_s_memtime();
 #endif
@@ -1660,6 +1668,9 @@ __device__ __forceinline__ void sa_span_doc_fused_body(const SpanDocParams& p, c
             }
         } else if (valid && !p.touched && !ranked) {
             p.counts[doc] = 0.f;
+        }
+        if constexpr (FILT) {
+            if (valid) valid = ((sa_glob(p.rank.filt)[doc >> 6] >> (doc & 63u)) & 1ull) != 0ull;
         }
         *valid_out = valid;
         return doc;
@@ -1956,7 +1967,7 @@ struct SpanSlot { u32 job, round; };   // eight blocks of a shared launch: job (
 // in the launch's order: phrases over the same frequent term) take turns, round after round: only a few blocks of a phrase are
 // resident at a time, and the ones that follow find the phrase's ranking bounds (SpanRankCtx::slots) already raised -- with a
 // phrase's blocks back to back all of them ranked against empty bounds, every wave of a heavy phrase took the exact top-k path.
-template <int TT, int NTAB>
+template <int TT, int NTAB, bool FILT>
 __global__ void __launch_bounds__(SA_SPAN_FT) sa_k_span_doc_fused_multi(const SpanDocParams* __restrict__ jobs, const SpanSlot* __restrict__ work) {
     const SpanSlot w = work[blockIdx.x >> 3];
     // (a reference, not a copy: a private copy of the job lives in scratch -- its term arrays are indexed at run time -- and
@@ -1965,7 +1976,7 @@ __global__ void __launch_bounds__(SA_SPAN_FT) sa_k_span_doc_fused_multi(const Sp
     const u32 per = (p.n_blocks + 7u) >> 3;
     const u32 wb = (blockIdx.x & 7u) * per + w.round;
     if (wb >= p.n_blocks) return;
-    sa_span_doc_fused_body<TT, NTAB>(p, wb);
+    sa_span_doc_fused_body<TT, NTAB, FILT>(p, wb);
 }
 
 // ---- B slop phrases in SHARED launches (phrase batches, BASELINE config 5) ------------------------------------------
@@ -2575,9 +2586,18 @@ int sa_span_counts_batch(sa_index* ix, hipStream_t st, int n, const u32* const* 
         const long long tw = sa_opt(ix->opts.span_tab_waves, dblocks[c] > 4u * (u32)ix->n_cus ? SA_SPAN_NTAB_BATCH : SA_SPAN_NTAB);
         const bool few = tw < SA_SPAN_NTAB;
         if (sa_opt(ix->opts.trace, 0)) fprintf(stderr, "sa_span_counts_batch: doc-parallel launch of %u phrases, %u blocks, %d table waves per block\n", cnt, dblocks[c], few ? SA_SPAN_NTAB_BATCH : SA_SPAN_NTAB);
+        // (the filtered instantiation: only where the blocks rank themselves -- count vectors are filtered by the ranking launch)
+        const bool filt = fused_rank && rank->filt != nullptr;
         sa_span_doc_by_terms(c + 2, [&](auto tt) {
-            if (few) hipLaunchKernelGGL((sa_k_span_doc_fused_multi<decltype(tt)::value, SA_SPAN_NTAB_BATCH>), dim3(dblocks[c]), dim3(SA_SPAN_FT), pad, st, jc, wc);
-            else hipLaunchKernelGGL((sa_k_span_doc_fused_multi<decltype(tt)::value, SA_SPAN_NTAB>), dim3(dblocks[c]), dim3(SA_SPAN_FT), pad, st, jc, wc);
+            constexpr int TTc = decltype(tt)::value;
+            const dim3 grid(dblocks[c]), blk(SA_SPAN_FT);
+            if (few) {
+                if (filt) hipLaunchKernelGGL((sa_k_span_doc_fused_multi<TTc, SA_SPAN_NTAB_BATCH, true>), grid, blk, pad, st, jc, wc);
+                else hipLaunchKernelGGL((sa_k_span_doc_fused_multi<TTc, SA_SPAN_NTAB_BATCH, false>), grid, blk, pad, st, jc, wc);
+            } else {
+                if (filt) hipLaunchKernelGGL((sa_k_span_doc_fused_multi<TTc, SA_SPAN_NTAB, true>), grid, blk, pad, st, jc, wc);
+                else hipLaunchKernelGGL((sa_k_span_doc_fused_multi<TTc, SA_SPAN_NTAB, false>), grid, blk, pad, st, jc, wc);
+            }
         });
     }
     SA_HIP(hipGetLastError());

@@ -446,8 +446,16 @@ class DeviceIndex(_options.OptionsMixin):
         return QueryQueue(self, n_queries, n_terms, k=k, k1=k1, b=b, depth=depth, opts=opts)
 
     def phrase_batch(self, phrases: Sequence[Sequence[int]], k: int = 10, k1: float = 1.2, b: float = 0.75,
-                     idf: Optional[np.ndarray] = None, slop=0, opts=None) -> "PhraseBatch":
-        return PhraseBatch(self, phrases, k=k, k1=k1, b=b, idf=idf, slop=slop, opts=opts)
+                     idf: Optional[np.ndarray] = None, slop=0, opts=None, filter: Optional["DocFilter"] = None) -> "PhraseBatch":
+        """a resident phrase top-k batch; ``filter``: a ``DocFilter`` of this index the batch ranks inside (``PhraseBatch.set_doc_filter``)"""
+        bt = PhraseBatch(self, phrases, k=k, k1=k1, b=b, idf=idf, slop=slop, opts=opts)
+        if filter is not None:
+            try:
+                bt.set_doc_filter(filter)
+            except Exception:
+                bt.close()
+                raise
+        return bt
 
     # -- multi-GPU
     def comm_init(self, rank: int, nranks: int, unique_id: bytes):
@@ -834,6 +842,14 @@ class PhraseBatch(QueryBatch):
         if (slops < 0).any():
             raise ValueError("slop must be >= 0")
         return as_u32(terms), n_terms, slops, as_f32(idf)
+
+    def set_doc_filter(self, filter: Optional["DocFilter"]):
+        """rank inside ``filter`` (a ``DocFilter`` of this batch's index) from the next run on; ``None``: the whole index again.
+        Every phrase returns the top-k of its unfiltered scores with the excluded docs' scores set to 0; persists across ``reset``
+        (``sa_phrase_batch_set_filter``; the inherited ``set_filter`` is the BM25 batches' call and refuses a phrase batch)"""
+        if filter is not None and not isinstance(filter, DocFilter):
+            raise TypeError("set_doc_filter takes a DocFilter or None")
+        self._call("sa_phrase_batch_set_filter", self._h, filter._need() if filter is not None else None)
 
     def reset(self, phrases: Sequence[Sequence[int]], idf: Optional[np.ndarray] = None, slop=0):
         """A new set of B phrases (none longer than the batch's max_terms) in this batch: ``sa_phrase_batch_reset``."""

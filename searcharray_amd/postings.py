@@ -839,10 +839,13 @@ class SearchArray(ExtensionArray):
             raise ValueError("filters are built on the whole indexed array, not on a slice")
         return self._core.device().term_filter(self._term_id(self._check_token_arg(token)))
 
-    def search_phrases(self, phrases, k: int = 10, similarity=default_bm25, devices=None, slop=0) -> Tuple[np.ndarray, np.ndarray]:
+    def search_phrases(self, phrases, k: int = 10, similarity=default_bm25, devices=None, slop=0, filter=None) -> Tuple[np.ndarray, np.ndarray]:
         """Like :meth:`search`, each query a phrase: the top-``k`` of ``arr.score(phrase, slop=slop)`` (``slop``: one
-        value or one per phrase).  Any phrase ``score`` takes is fine -- repeated tokens, long phrases, slop."""
-        return self._topk(phrases, k, similarity, phrases=True, devices=devices, slop=slop)
+        value or one per phrase).  Any phrase ``score`` takes is fine -- repeated tokens, long phrases, slop.
+        ``filter``: what :meth:`search` takes -- a boolean mask, row ids, or a filter from :meth:`doc_filter` / :meth:`term_filter` --
+        with the same meaning: the top-``k`` of ``arr.score(phrase, slop=slop)`` with the excluded rows' scores set to 0, scored
+        with the statistics of the whole array."""
+        return self._topk(phrases, k, similarity, phrases=True, devices=devices, slop=slop, filter=filter)
 
     def _topk(self, queries, k, similarity, phrases, devices=None, slop=0, filter=None, mm=None, q_op="OR", occur=None):
         if getattr(similarity, "kind", None) != "bm25":
@@ -896,7 +899,10 @@ class SearchArray(ExtensionArray):
                     f = own = dev.doc_filter(mask=filter.to_mask())
                 else:
                     f = own = dev.doc_filter(mask=fmask) if fmask is not None else dev.doc_filter(rows=frows)
-                batch.set_filter(f)
+                if phrases:
+                    batch.set_doc_filter(f)
+                else:
+                    batch.set_filter(f)
             batch.run()
             return batch.fetch()
         finally:

@@ -192,7 +192,8 @@ class ShardedIndex:
             raise
         return bt
 
-    def phrase_batch(self, phrases, k: int = 10, k1: float = 1.2, b: float = 0.75, slop=0, opts=None) -> "ShardedBatch":
+    def phrase_batch(self, phrases, k: int = 10, k1: float = 1.2, b: float = 0.75, slop=0, opts=None,
+                     filter: Optional["ShardedDocFilter"] = None) -> "ShardedBatch":
         ct = _lib.ctypes
         B = len(phrases)
         if B == 0:
@@ -213,7 +214,14 @@ class ShardedIndex:
             self.api.call("sa_sharded_phrase_batch_create", self._h, _lib.p_u32(_lib.as_u32(terms)),
                           n_terms.ctypes.data_as(ct.POINTER(ct.c_int32)), slops.ctypes.data_as(ct.POINTER(ct.c_int32)),
                           _lib.p_f32(_lib.as_f32(idf)), B, T, int(k), np.float32(k1), np.float32(b), ct.byref(h))
-        return ShardedBatch(self, h, B, int(k), opts=_options.Options(self._opts, opts))
+        bt = ShardedBatch(self, h, B, int(k), opts=_options.Options(self._opts, opts))
+        if filter is not None:
+            try:
+                bt.set_doc_filter(filter)
+            except Exception:
+                bt.close()
+                raise
+        return bt
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -285,6 +293,14 @@ class ShardedBatch(_options.OptionsMixin):
         if filter is not None and not isinstance(filter, ShardedDocFilter):
             raise TypeError("set_filter takes a filter of ShardedIndex.doc_filter or None")
         self._call("sa_sharded_batch_set_filter", self._h, filter._need() if filter is not None else None)
+
+    def set_doc_filter(self, filter: Optional[ShardedDocFilter]):
+        """the same for a phrase batch (``ShardedIndex.phrase_batch``): ``sa_sharded_phrase_batch_set_filter``"""
+        if filter is not None and not isinstance(filter, ShardedDocFilter):
+            raise TypeError("set_doc_filter takes a filter of ShardedIndex.doc_filter or None")
+        if self.T is not None:
+            raise ValueError("set_doc_filter takes a phrase batch (BM25 batches: set_filter)")
+        self._call("sa_sharded_phrase_batch_set_filter", self._h, filter._need() if filter is not None else None)
 
     def set_min_match(self, values):
         """minimum-should-match, the same per-query values on every shard's batch (``QueryBatch.set_min_match``); ``None`` clears them"""

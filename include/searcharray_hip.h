@@ -114,6 +114,7 @@ typedef struct sa_options {
     int64_t io_threads;      /* file threads */
     int64_t trace;           /* 1: route decisions to stderr */
     int64_t stage_pipe;      /* staged-tile route: the next tile's layout built while the stage loads are in flight: 1 wherever eligible, 0 never; unset: where eligible from 256 staged terms on */
+    int64_t fields_cand_mb;  /* candidate scratch of a fields batch (Part 4b) in MiB at most (default 256): a query set that needs more runs in slices of queries */
 } sa_options_t;
 void sa_options_init(sa_options_t* opts);                                  /* all unset */
 int sa_options_set(sa_options_t* opts, const char* name, int64_t value);
@@ -689,6 +690,42 @@ int sa_vec_field_finish(const sa_vec_t* fsum32, const sa_vec_t* fmax32, float ti
 int sa_vec_add32(sa_vec_t* dst32, const sa_vec_t* src32, int first);
 int sa_vec_add_where(sa_vec_t* dst, const sa_vec_t* extra32, const sa_vec_t* mask);
 int sa_vec_count_where(const sa_vec_t* tf32, const sa_vec_t* mask, uint64_t* out);
+
+/* ------------------------------------------------------------------------------------- */
+/* Part 4b -- batches of multi-field (edismax, term-centric) queries (csrc/sa_fields.hip)  */
+/* ------------------------------------------------------------------------------------- */
+/* What Part 4 does per query with dense vectors -- per clause t and field f the float32 BM25 vector of the clause's term in that
+ * field (x the field's boost), sum and max over the fields in float64, clause = max + (sum - max) * tie, total += clause,
+ * cnt += clause > 0, total = 0 where cnt < need, then sa_vec_topk -- for B queries in one pass over (tile, query) items, with the same
+ * operations in the same order on the same values: per query the result is bit-identical, and no [n_docs] vector is written.
+ * A fields batch spans F (1 .. 8) indexes -- the columns of a frame -- on one device, with the same n_docs, doc_base 0 and no
+ * communicator; field f scores with BM25(k1[f], b[f]) over that index's impact stream and multiplies by boost[f] when has_boost[f].
+ * A field without postings or with avg_doc_len 0 contributes zeros (as sa_index_bm25_dense); a field whose impact stream cannot be had
+ * (option impact = 0, device memory short) -> SA_ERR_UNSUPPORTED: answer such frames query by query with Part 4.
+ * The batch owns a stream and its scratch; it reads the indexes' immutable arrays only, so it runs beside anything else the indexes do.
+ * Calls on one batch are serialised; different batches are independent. */
+typedef struct sa_fields_batch sa_fields_batch_t;
+int sa_fields_batch_create(sa_index_t* const* fields, int n_fields, const float* k1, const float* b, const float* boost,
+                           const int32_t* has_boost, sa_fields_batch_t** out);
+/* A query set: terms u32[n_queries][n_clauses][n_fields] (0xFFFFFFFF: the field lacks the token, or a padding clause), weights
+ * f32[same shape] (the float32 idf the host forms, similarity.py:19-21), need u32[n_queries] (minimum-should-match: clauses with a
+ * value > 0 a document needs), one tie for the set; 1 <= n_clauses <= 32, 1 <= k <= 1024.  One asynchronous copy behind the runs
+ * in flight; nothing is allocated when the shape fits what the batch has held before.  Fetch a run's results before loading the next set. */
+int sa_fields_batch_set_queries(sa_fields_batch_t* batch, const uint32_t* terms, const float* weights, const uint32_t* need,
+                                int n_queries, int n_clauses, int k, double tie);
+/* rank inside `filter` from the next run on (NULL: all documents): a filter of ANY index on the batch's device with the same n_docs
+ * (the rows of a frame's columns align); excluded documents score 0, tiles whose filter blocks are empty are not read */
+int sa_fields_batch_set_filter(sa_fields_batch_t* batch, sa_filter_t* filter);
+/* score and rank the loaded set on the batch's stream (sync != 0: wait for it).  Candidate scratch is bounded by the option
+ * fields_cand_mb: a set that needs more runs in slices of queries, same results. */
+int sa_fields_batch_run(sa_fields_batch_t* batch, int sync);
+/* scores f64[n_queries][k], rows u64[n_queries][k] (score descending, then row ascending; slots past the hits: 0 and 2^64-1),
+ * found u64[n_queries] (documents with a score > 0 inside the filter, whatever k is; may be NULL).  Waits for the run. */
+int sa_fields_batch_fetch(sa_fields_batch_t* batch, double* scores_out, uint64_t* rows_out, uint64_t* found_out);
+/* HIP-event time (ms) of the last run's score and merge kernels, the algorithmic bytes of the loaded set (8 x the postings of every
+ * (query, clause, field) term) and the slices the last run took; any pointer may be NULL */
+int sa_fields_batch_profile(sa_fields_batch_t* batch, double* kernel_ms_out, uint64_t* alg_bytes_out, uint32_t* slices_out);
+int sa_fields_batch_destroy(sa_fields_batch_t* batch);
 
 #ifdef __cplusplus
 }

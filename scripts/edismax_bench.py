@@ -7,10 +7,9 @@ strings: what makes 10 M docs practical; the documents are the same); --no-host-
 10 M docs).  --out FILE appends the JSON line to FILE (profiles/edismax_topk.jsonl)."""
 import argparse, json, os, sys, time
 import numpy as np
-import pandas as pd
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from searcharray_amd import SearchArray, synth
 from searcharray_amd.solr import edismax, edismax_search
+from edismax_frame import build_frame
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--docs", type=int, default=500_000)
@@ -19,40 +18,8 @@ ap.add_argument("--out", default=None)
 ap.add_argument("--from-tokens", action="store_true")
 ap.add_argument("--no-host-leg", action="store_true")
 args = ap.parse_args()
-D, V = args.docs, 50_000
-names = np.array([f"t{i}" for i in range(V)])
-frames = {}
-
-
-def array_from_tokens(lens, terms, starts):
-    """the SearchArray that SearchArray.index builds from the joined strings, from the token ids themselves"""
-    from searcharray_amd.indexing import HostIndex
-    from searcharray_amd.postings import _IndexCore, ws_tokenizer
-    from searcharray_amd.term_dict import TermDict
-    present = np.unique(terms)                                   # (index() numbers the terms in order of first appearance; ids are
-    term_dict = TermDict()                                       #  internal, so any numbering gives the same scores)
-    term_dict.add_terms([str(t) for t in names[present]])
-    remap = np.zeros(V, dtype=np.uint32)
-    remap[present] = np.arange(len(present), dtype=np.uint32)
-    host = HostIndex(term_dict, lens.astype(np.float32), tokens=np.ascontiguousarray(remap[terms]),
-                     doc_ptr=np.ascontiguousarray(starts, dtype=np.uint64))
-    arr = SearchArray.__new__(SearchArray)
-    arr.avoid_copies, arr.tokenizer, arr._core, arr._rows = True, ws_tokenizer, _IndexCore(host), None
-    return arr
-
-
-for field, seed_off in (("title", 0), ("body", 1)):
-    lens, terms = synth.zipf_batch_tokens(seed_off, D, V, fast=True)
-    if field == "title":
-        lens = np.maximum(1, lens // 4)
-        starts = np.concatenate([[0], np.cumsum(lens)])
-        terms = terms[:starts[-1]]
-    starts = np.concatenate([[0], np.cumsum(lens)])
-    if args.from_tokens:
-        frames[field] = array_from_tokens(lens, terms[:starts[-1]], starts)
-    else:
-        frames[field] = SearchArray.index([" ".join(names[terms[starts[i]:starts[i + 1]]]) for i in range(D)])
-frame = pd.DataFrame(frames)
+D = args.docs
+frame = build_frame(D, args.from_tokens)
 params = dict(q="t3 t40 t7", qf=["title^3", "body"], pf=["body"], pf2=["title", "body"], mm="2<75%", tie=0.2)
 out = {"docs": D, "frame": "tokens" if args.from_tokens else "strings"}
 res = {}

@@ -184,6 +184,14 @@ PROTOTYPES = {
     "sa_vec_add32": (c_int, [c_void_p, c_void_p, c_int]),
     "sa_vec_add_where": (c_int, [c_void_p, c_void_p, c_void_p]),
     "sa_vec_count_where": (c_int, [c_void_p, c_void_p, u64p]),
+    # Part 4b: batches of multi-field queries
+    "sa_fields_batch_create": (c_int, [POINTER(c_void_p), c_int, f32p, f32p, f32p, POINTER(ctypes.c_int32), POINTER(c_void_p)]),
+    "sa_fields_batch_set_queries": (c_int, [c_void_p, u32p, f32p, u32p, c_int, c_int, c_int, c_double]),
+    "sa_fields_batch_set_filter": (c_int, [c_void_p, c_void_p]),
+    "sa_fields_batch_run": (c_int, [c_void_p, c_int]),
+    "sa_fields_batch_fetch": (c_int, [c_void_p, POINTER(c_double), u64p, u64p]),
+    "sa_fields_batch_profile": (c_int, [c_void_p, POINTER(c_double), u64p, u32p]),
+    "sa_fields_batch_destroy": (c_int, [c_void_p]),
     # Part 3
     "sa_comm_unique_id": (c_int, [ctypes.c_char_p, c_int]),
     "sa_index_comm_init": (c_int, [c_void_p, c_int, c_int, ctypes.c_char_p, c_int]),

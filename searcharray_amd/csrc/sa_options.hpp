@@ -74,7 +74,9 @@
     /* ---- diagnostics */                                                                                                         \
     X(trace)           /* 1: route decisions to stderr */                                                                           \
     /* ---- appended (the struct is versioned by its size: new fields go last) */                                                  \
-    X(stage_pipe)      /* staged-tile route: the next tile's layout built while the stage loads are in flight: 1 wherever eligible, 0 never; unset: where eligible from 256 staged terms on */
+    X(stage_pipe)      /* staged-tile route: the next tile's layout built while the stage loads are in flight: 1 wherever eligible, 0 never; unset: where eligible from 256 staged terms on */ \
+    /* ---- multi-field batches (sa_fields.hip) */                                                                                 \
+    X(fields_cand_mb)  /* candidate scratch of a fields batch in MiB at most (default 256): a query set that needs more runs in slices of queries */
 
 struct sa_options_fields {
     uint64_t struct_size;

@@ -36,7 +36,12 @@ extern "C" int sa_vec_create(int device, uint64_t n, int is_f64, sa_vec_t** out)
     v->device = device; v->n = n; v->f64 = is_f64 ? 1 : 0;
     const size_t bytes = (size_t)(n ? n : 1) * (is_f64 ? 8 : 4);
     if (hipMalloc(&v->d, bytes) != hipSuccess) { delete v; sa_set_error("hipMalloc failed (vector)"); return SA_ERR_HIP; }
-    SA_HIP(hipMemset(v->d, 0, bytes));
+    // (on the vectors' own stream, then waited for: a plain hipMemset / device-to-device hipMemcpy runs on the null stream, which a
+    //  non-blocking stream does not wait for -- the kernels of the next call could overtake it)
+    hipStream_t st = sa_vec_stream(device);
+    if (hipMemsetAsync(v->d, 0, bytes, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+        hipFree(v->d); delete v; sa_set_error("hipMemset failed (vector)"); return SA_ERR_HIP;
+    }
     *out = v;
     return SA_OK;
 }
@@ -53,21 +58,27 @@ extern "C" int sa_vec_destroy(sa_vec_t* v) {
 extern "C" int sa_vec_zero(sa_vec_t* v) {
     SA_ARG(v, "null vector");
     SA_HIP(hipSetDevice(v->device));
-    SA_HIP(hipMemset(v->d, 0, (size_t)v->n * (v->f64 ? 8 : 4)));
+    hipStream_t st = sa_vec_stream(v->device);
+    SA_HIP(hipMemsetAsync(v->d, 0, (size_t)v->n * (v->f64 ? 8 : 4), st));
+    SA_HIP(hipStreamSynchronize(st));
     return SA_OK;
 }
 
 extern "C" int sa_vec_copy(sa_vec_t* dst, const sa_vec_t* src) {
     SA_ARG(dst && src && dst->n == src->n && dst->f64 == src->f64 && dst->device == src->device, "vectors differ");
     SA_HIP(hipSetDevice(dst->device));
-    if (dst->n) SA_HIP(hipMemcpy(dst->d, src->d, (size_t)dst->n * (dst->f64 ? 8 : 4), hipMemcpyDeviceToDevice));
+    hipStream_t st = sa_vec_stream(dst->device);
+    if (dst->n) SA_HIP(hipMemcpyAsync(dst->d, src->d, (size_t)dst->n * (dst->f64 ? 8 : 4), hipMemcpyDeviceToDevice, st));
+    SA_HIP(hipStreamSynchronize(st));
     return SA_OK;
 }
 
 extern "C" int sa_vec_fetch(sa_vec_t* v, void* host_out) {
     SA_ARG(v && (host_out || v->n == 0), "null argument");
     SA_HIP(hipSetDevice(v->device));
-    if (v->n) SA_HIP(hipMemcpy(host_out, v->d, (size_t)v->n * (v->f64 ? 8 : 4), hipMemcpyDeviceToHost));
+    hipStream_t st = sa_vec_stream(v->device);
+    if (v->n) SA_HIP(hipMemcpyAsync(host_out, v->d, (size_t)v->n * (v->f64 ? 8 : 4), hipMemcpyDeviceToHost, st));
+    SA_HIP(hipStreamSynchronize(st));
     return SA_OK;
 }
 

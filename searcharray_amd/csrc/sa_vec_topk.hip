@@ -292,7 +292,9 @@ static int sa_vec_topk_scratch_get(sa_vec* v) {
 extern "C" int sa_vec_store(sa_vec_t* v, const void* host_in) {
     SA_ARG(v && (host_in || v->n == 0), "null argument");
     SA_HIP(hipSetDevice(v->device));
-    if (v->n) SA_HIP(hipMemcpy(v->d, host_in, (size_t)v->n * (v->f64 ? 8 : 4), hipMemcpyHostToDevice));
+    hipStream_t st = sa_vec_stream(v->device);                            // (the vectors' stream, waited for: see sa_vec_create)
+    if (v->n) SA_HIP(hipMemcpyAsync(v->d, host_in, (size_t)v->n * (v->f64 ? 8 : 4), hipMemcpyHostToDevice, st));
+    SA_HIP(hipStreamSynchronize(st));
     return SA_OK;
 }
 

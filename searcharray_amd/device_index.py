@@ -859,6 +859,93 @@ class PhraseBatch(QueryBatch):
                       slops.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), p_f32(idf))
 
 
+class FieldsBatch:
+    """Batches of multi-field (edismax, term-centric) queries over F ``DeviceIndex`` es -- the columns of a frame -- ranked in one
+    pass (Part 4b of the C ABI, csrc/sa_fields.hip).  ``k1`` / ``b``: one BM25 parameter pair per field; ``boosts``: one per field,
+    ``None`` for a field without one.  ``set_queries`` loads a set (one async copy), ``run`` scores it, ``fetch`` returns
+    ``(scores float64[B][k], rows uint64[B][k], found uint64[B])``: per query what ``solr.edismax_search`` returns for it, bit for bit.
+    The object is reusable: a new set of a shape it has held before allocates nothing.  Options (``fields_cand_mb``, ``trace``) are read
+    when the object is created: the first index's, ``opts`` and the thread's scoped options."""
+
+    def __init__(self, indexes: Sequence[DeviceIndex], k1: Sequence[float], b: Sequence[float],
+                 boosts: Optional[Sequence[Optional[float]]] = None, opts=None):
+        indexes = list(indexes)
+        if not indexes:
+            raise ValueError("a FieldsBatch needs at least one index")
+        self.indexes = indexes
+        self.api = indexes[0].api
+        self.F = len(indexes)
+        boosts = [None] * self.F if boosts is None else list(boosts)
+        if len(k1) != self.F or len(b) != self.F or len(boosts) != self.F:
+            raise ValueError("k1, b and boosts take one entry per field")
+        handles = (ctypes.c_void_p * self.F)(*[ix._h for ix in indexes])
+        k1a, ba = as_f32(list(k1)), as_f32(list(b))
+        boost = as_f32([1.0 if x is None else x for x in boosts])
+        has = np.ascontiguousarray([0 if x is None else 1 for x in boosts], dtype=np.int32)
+        self.B = self.T = self.k = 0
+        self._h = ctypes.c_void_p()
+        base = _options.Options(indexes[0]._opts_base, opts)
+        with _options.creating(self.api, base):
+            self.api.call("sa_fields_batch_create", handles, self.F, p_f32(k1a), p_f32(ba), p_f32(boost),
+                          has.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), ctypes.byref(self._h))
+        for ix in indexes:                       # (the batch reads every index's arrays: closed before any of them goes)
+            ix._track(self)
+
+    def set_queries(self, terms, weights, need, k: int = 10, tie: float = 0.0):
+        """``terms`` int[B][T][F] (anything outside a field's vocabulary: the field lacks the token), ``weights`` float32[B][T][F]
+        (the idf the host forms), ``need`` int[B] (clauses with a value > 0 a row needs)"""
+        t = np.asarray(terms, dtype=np.int64)
+        if t.ndim != 3 or t.shape[2] != self.F or t.shape[0] < 1 or not 1 <= t.shape[1] <= 32:
+            raise ValueError(f"terms must be [B][T][{self.F}] term ids with B >= 1 and 1 <= T <= 32")
+        k = int(k)
+        if not 1 <= k <= 1024:
+            raise ValueError("k must be in 1 .. 1024")
+        n_terms = np.asarray([ix.n_terms for ix in self.indexes], dtype=np.int64)
+        tu = as_u32(np.where((t >= 0) & (t < n_terms), t, NO_TERM))
+        w = as_f32(weights)
+        nd = np.ascontiguousarray(need, dtype=np.uint32)
+        if w.shape != t.shape or nd.shape != (t.shape[0],):
+            raise ValueError("weights has the shape of terms, need one entry per query")
+        self.api.call("sa_fields_batch_set_queries", self._h, p_u32(tu), p_f32(w), p_u32(nd), t.shape[0], t.shape[1], k, float(tie))
+        self.B, self.T, self.k = t.shape[0], t.shape[1], k
+
+    def set_filter(self, filter: Optional["DocFilter"]):
+        """rank inside ``filter`` from the next run on (``None``: every row): a ``DocFilter`` of ANY index on the same device with the
+        same number of documents"""
+        if filter is not None and not isinstance(filter, DocFilter):
+            raise TypeError("set_filter takes a DocFilter or None")
+        self.api.call("sa_fields_batch_set_filter", self._h, filter._need() if filter is not None else None)
+
+    def run(self, sync: bool = True):
+        self.api.call("sa_fields_batch_run", self._h, 1 if sync else 0)
+
+    def fetch(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        scores = np.empty((self.B, self.k), dtype=np.float64)
+        rows = np.empty((self.B, self.k), dtype=np.uint64)
+        found = np.empty(self.B, dtype=np.uint64)
+        self.api.call("sa_fields_batch_fetch", self._h, scores.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), p_u64(rows), p_u64(found))
+        return scores, rows, found
+
+    def profile(self) -> Tuple[float, int, int]:
+        """(HIP-event ms of the last run's kernels, algorithmic bytes of the loaded set, slices the last run took)"""
+        ms = _lib.c_double(0)
+        alg = _lib.c_uint64(0)
+        slices = _lib.c_uint32(0)
+        self.api.call("sa_fields_batch_profile", self._h, ctypes.byref(ms), ctypes.byref(alg), ctypes.byref(slices))
+        return ms.value, int(alg.value), int(slices.value)
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self.api.sa_fields_batch_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class DeviceVec:
     """A dense per-doc vector in HBM (float64, or 32-bit: float32 values / uint32 counters); Part 4 of
     the C ABI.  Used by ``searcharray_amd.solr`` to combine multi-field scores without leaving the device."""

@@ -542,7 +542,7 @@ def edismax_search(frame: pd.DataFrame,
     and ``mm`` and the phrase-boost phases (which use the docs the main query matched) do not see the filter.  This is not the
     reference's slice semantics (``frame[rows]`` recomputes docfreq inside the slice).
 
-    Not covered: lists of queries per call, sharded frames (``devices=``), and filters for phrase batches and the queue."""
+    A list of queries per call: :func:`edismax_search_batch`.  Not covered: sharded frames (``devices=``), and filters for the queue."""
     k = int(k)
     if not 1 <= k <= 1024:
         raise ValueError("k must be in 1 .. 1024")
@@ -567,6 +567,142 @@ def edismax_search(frame: pd.DataFrame,
         return SearchHits(*scores_v.topk(k, filter=filt), explain)
     finally:
         comb.close()
+        if own is not None:
+            own.close()
+
+
+_BATCH_MAX_FIELDS = 8           # a fields batch spans at most this many columns (sa_fields_batch_create)
+_BATCH_MAX_TERMS = 32           # ... and a query at most this many clauses (SA_MAX_QTERMS)
+
+
+def _fields_batch_inputs(plans: List[_Plan], picked: Sequence[int]):
+    """what a fields batch takes for the queries ``plans[i], i in picked`` (term-centric, 1 .. 32 terms, same fields): term ids
+    int64[B][T][F] (-1: the field lacks the token, or a padding clause), weights float32[B][T][F], need uint32[B]"""
+    from .device_index import compute_idf
+    F = len(plans[picked[0]].fields)
+    T = max(plans[i].n_terms for i in picked)
+    terms = np.full((len(picked), T, F), -1, dtype=np.int64)
+    weights = np.zeros((len(picked), T, F), dtype=np.float32)
+    need = np.zeros(len(picked), dtype=np.uint32)
+    seen: Dict[Tuple[int, str], Tuple[int, np.float32]] = {}
+    for row, i in enumerate(picked):
+        plan = plans[i]
+        need[row] = parse_min_should_match(plan.n_terms, spec=plan.mm)
+        for j, f in enumerate(plan.fields):
+            for posn, tok in enumerate(f.terms):
+                hit = seen.get((j, tok))
+                if hit is None:
+                    # (what _DeviceCombiner.score_into passes: the id, and the float32 idf of the token's docfreq)
+                    idf = np.float32(compute_idf(f.array.corpus_size, np.asarray([f.array.docfreq(tok)])))
+                    hit = seen[(j, tok)] = (f.array._term_id(tok), idf)
+                terms[row, posn, j], weights[row, posn, j] = hit
+    return terms, weights, need
+
+
+def _fields_batch_open(fields: List[_Field]):
+    """a ``FieldsBatch`` (Part 4b of the C ABI, csrc/sa_fields.hip) over the fields' device indexes, with their BM25 parameters and boosts"""
+    from .device_index import FieldsBatch
+    return FieldsBatch([f.array._core.device() for f in fields], [np.float32(f.similarity.k1) for f in fields],
+                       [np.float32(f.similarity.b) for f in fields], [f.boost for f in fields])
+
+
+def _fields_batch_hits(plans: List[_Plan], picked: List[int], k: int, tie: float, filt) -> Optional[List[SearchHits]]:
+    """the queries ``plans[i], i in picked`` ranked by ONE fields batch; None when the library cannot build one for these fields
+    (no impact stream): the caller then answers them one by one"""
+    from ._lib import SearchArrayHipError
+    terms, weights, need = _fields_batch_inputs(plans, picked)
+    try:
+        fb = _fields_batch_open(plans[picked[0]].fields)
+    except SearchArrayHipError:
+        return None
+    try:
+        if filt is not None:
+            fb.set_filter(filt)
+        fb.set_queries(terms, weights, need, k=k, tie=tie)
+        fb.run(sync=False)
+        scores, rows, found = fb.fetch()
+    finally:
+        fb.close()
+    return [SearchHits(scores[row].copy(), rows[row].copy(), int(found[row]),
+                       _explain_main(plans[i].fields, plans[i].n_terms, plans[i].mm, True)) for row, i in enumerate(picked)]
+
+
+def edismax_search_batch(frame: pd.DataFrame,
+                         queries: Sequence[str],
+                         qf: List[str],
+                         k: int = 10,
+                         fq=None,
+                         mm: Optional[Union[str, int]] = None,
+                         pf: Optional[List[str]] = None,
+                         pf2: Optional[List[str]] = None,
+                         pf3: Optional[List[str]] = None,
+                         ps2: int = 0,
+                         ps3: int = 0,
+                         ps: int = 0,
+                         tie: float = 0.0,
+                         q_op: str = "OR",
+                         similarity: Union[Similarity, Dict[str, Similarity]] = default_bm25,
+                         use_device: Optional[bool] = None) -> List[SearchHits]:
+    """:func:`edismax_search` for a list of queries: ``hits[i]`` equals ``edismax_search(frame, queries[i], qf, k=k, fq=fq, ...)``
+    field by field -- ``scores`` (dtype included), ``rows``, ``found``, ``explain``.  The other arguments are those of
+    ``edismax_search`` and apply to every query; ``mm`` resolves against each query's own number of terms.
+
+    Term-centric queries of 1 .. 32 terms are scored and ranked by ONE launch sequence over all of them (``FieldsBatch``: every
+    (tile, query) item forms the float64 edismax score of its documents in LDS from the fields' postings, applies ``mm`` and
+    ``fq`` and selects its best ``k``; a merge per query follows), with no per-row vector written for any query -- whenever the
+    device route applies (``edismax``'s rule; ``use_device`` is not False), no ``pf`` / ``pf2`` / ``pf3`` is given and ``qf``
+    names at most 8 fields.  Every other query -- field-centric ones, more than 32 terms -- or, when the condition is one of the
+    call's, the whole list goes through ``edismax_search`` one by one and lands at its index; nothing raises because of the
+    route and nothing differs.  An ``fq`` given as a mask or row ids becomes ONE device filter for the whole call, closed
+    afterwards; a caller's ``DocFilter`` stays open.  ``k`` and ``fq`` are checked before anything is launched.
+
+    Not covered: sharded frames (``devices=``), field-centric queries and phrase boosts on the batch kernel (they take the
+    per-query route), bounds or pruning across tiles (every item scores its tile exhaustively), and the query-set queue."""
+    k = int(k)
+    if not 1 <= k <= 1024:
+        raise ValueError("k must be in 1 .. 1024")
+    queries = list(queries)
+    plans = [_plan(frame, q, qf, mm, pf, pf2, pf3, q_op, similarity) for q in queries]
+    n = len(frame)
+    if isinstance(fq, DocFilter):
+        if fq.index.n_docs != n:
+            raise ValueError(f"fq covers {fq.index.n_docs} documents, the frame has {n} rows")
+        mask = None
+    else:
+        mask = _fq_mask(frame, fq)                                  # (checked before anything is launched)
+    if not plans:
+        return []
+    each = dict(k=k, mm=mm, pf=pf, pf2=pf2, pf3=pf3, ps2=ps2, ps3=ps3, ps=ps, tie=tie, q_op=q_op, similarity=similarity,
+                use_device=use_device)
+    fields = plans[0].fields                                        # (the fields are the call's; only their terms differ per query)
+    device = _DeviceCombiner.usable(fields, n) if use_device is None else bool(use_device)
+    if not device or not _DeviceCombiner.usable(fields, n):
+        # the host route, or a forced device route on a frame the combiner cannot take: exactly what edismax_search does with it
+        return [edismax_search(frame, q, qf, fq=fq if mask is None else mask, **each) for q in queries]
+    own = None                                                      # ONE filter for the whole call, made here from a mask or row ids
+    filt = fq
+    if mask is not None:
+        filt = own = fields[0].array._core.device().doc_filter(mask=mask)
+    try:
+        hits: List[Optional[SearchHits]] = [None] * len(queries)
+        picked: List[int] = []
+        if not (pf or pf2 or pf3) and len(fields) <= _BATCH_MAX_FIELDS:
+            for i, plan in enumerate(plans):
+                if plan.term_centric and all(len(f.terms) == plan.n_terms for f in plan.fields):
+                    if plan.n_terms == 0:                           # no clause, no hit: what the empty device vector ranks to
+                        hits[i] = SearchHits(np.zeros(k, dtype=np.float64), np.full(k, NO_DOC, dtype=np.uint64), 0,
+                                             _explain_main(plan.fields, 0, plan.mm, True))
+                    elif plan.n_terms <= _BATCH_MAX_TERMS:
+                        picked.append(i)
+        if picked:
+            got = _fields_batch_hits(plans, picked, k, tie, filt)
+            for i, h in zip(picked, got or []):
+                hits[i] = h
+        for i, q in enumerate(queries):
+            if hits[i] is None:
+                hits[i] = edismax_search(frame, q, qf, fq=filt, **each)
+        return hits
+    finally:
         if own is not None:
             own.close()
 

@@ -509,6 +509,31 @@ int sa_batch_host_times(sa_batch_t* batch, uint64_t out[4]);
 int sa_batch_seeds(sa_batch_t* batch, float* out);
 int sa_batch_destroy(sa_batch_t* batch);
 
+/* ---- Part 2d: HIT COUNTS AND FACET COUNTS (csrc/sa_facet.hip; the batch kernel: csrc/sa_bm25.hip sa_k_bm25_facet_tiles) -- Solr's
+ * `numFound` and `facet.field` for BM25 batches and device vectors, counted on the device: per query two counters and one u32 per
+ * category value leave it, never a score vector.  No reference counterpart (its callers fetch score() and count in numpy).
+ * A COLUMN is one int32 category code per document, resident on a device, immutable.
+ * codes[n_docs]: -1 = no value (pandas' Categorical code for NaN), else in [0, n_values); anything else -> SA_ERR_ARG.
+ * 1 <= n_values <= 2^20.  n_docs must be the index's (shard-local rows, like a filter mask).  Built on the index stream, complete on
+ * return.  Like a filter, a column belongs to a device and a length, and is accepted wherever the device and n_docs match (the
+ * rows of a frame's fields align; sa_vec_topk takes filters on that rule). */
+typedef struct sa_codes sa_codes_t;
+int sa_codes_create(sa_index_t* index, const int32_t* codes, uint64_t n_docs, uint32_t n_values, sa_codes_t** out);
+int sa_codes_destroy(sa_codes_t* codes);
+/* For every query of the BM25 batch, in CALLER query order, over the query set currently loaded and the batch's current filter /
+ * min-match / occur state:
+ *   found_out[i]   = documents whose final score is > 0 (what sa_batch_fetch could return for k = n_docs)
+ *   missing_out[i] = those of them with code -1
+ *   counts_out[i * n_values + c] = those of them with code c
+ * codes == NULL: found only (counts_out and missing_out ignored; either may be NULL).
+ * The matched set is by construction the one a run ranks: the same tile item scores the tile, applies the minimum-should-match / occur
+ * clear and the filter clear, and a histogram stands where the top-k selection would.  Exact: integer atomics, order-independent.
+ * Synchronous.  Runs on the batch's stream behind whatever is in flight; touches none of the top-k state: a run that has not
+ * been fetched returns the same results afterwards.
+ * SA_ERR_UNSUPPORTED: phrase batches; tile_docs outside 1024 / 2048 / 4096 / 8192.  SA_ERR_ARG: a column of another device or length;
+ * n_queries * n_values > 2^28.  Handles of the sharded index (Part 3b) and the query-set queue (Part 2c) have no such call. */
+int sa_batch_facet_counts(sa_batch_t* batch, sa_codes_t* codes, uint64_t* found_out, uint64_t* missing_out, uint32_t* counts_out);
+
 typedef struct sa_index_info {
     uint64_t n_docs, doc_base, corpus_size, n_words, n_postings;
     uint32_t n_terms, tile_docs, n_tiles, n_dir_terms;
@@ -671,6 +696,13 @@ int sa_vec_topk(sa_vec_t* v, sa_filter_t* filter, int k, void* scores_out, uint6
 /* diagnostics: the passes over the vector the last sa_vec_topk of `v` made (0: no call yet, or the last call read nothing: an
  * empty vector or an empty filter) */
 int sa_vec_topk_passes(const sa_vec_t* v, int* passes_out);
+/* Facet counts of a vector (Part 2d; csrc/sa_facet.hip): entries with value > 0 (NaN never counts) whose bit is set in `filter`
+ * (NULL: all) -- sa_vec_topk's eligibility -- counted as sa_batch_facet_counts counts a query: *found_out, *missing_out,
+ * counts_out[n_values]; codes == NULL: found only.  One streaming pass (float32 and float64 vectors; blocks of 1024 documents the
+ * filter leaves empty are not read).  The filter and the column must live on the vector's device and cover v->n documents, else
+ * SA_ERR_ARG.  Synchronous. */
+int sa_vec_facet_counts(sa_vec_t* v, sa_filter_t* filter, sa_codes_t* codes, uint64_t* found_out, uint64_t* missing_out,
+                        uint32_t* counts_out);
 /* the next dense call on `ix` from this thread writes (result * boost if has_boost) into out32 on the
  * device instead of to its host `out`; out32 == NULL clears a pending selection */
 int sa_index_select_vec(sa_index_t* ix, sa_vec_t* out32, float boost, int has_boost);

@@ -162,6 +162,11 @@ PROTOTYPES = {
     "sa_sharded_batch_set_min_match": (c_int, [c_void_p, u32p]),
     "sa_batch_set_occur": (c_int, [c_void_p, POINTER(ctypes.c_uint8)]),
     "sa_sharded_batch_set_occur": (c_int, [c_void_p, POINTER(ctypes.c_uint8)]),
+    # Part 2d: hit counts and facet counts
+    "sa_codes_create": (c_int, [c_void_p, POINTER(ctypes.c_int32), c_uint64, c_uint32, POINTER(c_void_p)]),
+    "sa_codes_destroy": (c_int, [c_void_p]),
+    "sa_batch_facet_counts": (c_int, [c_void_p, c_void_p, u64p, u64p, u32p]),
+    "sa_vec_facet_counts": (c_int, [c_void_p, c_void_p, c_void_p, u64p, u64p, u32p]),
     "sa_index_select_rows": (c_int, [c_void_p, u64p, c_uint64]),
     "sa_host_alloc": (c_int, [c_uint64, POINTER(c_void_p)]),
     "sa_host_free": (c_int, [c_void_p]),

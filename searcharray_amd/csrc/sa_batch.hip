@@ -6,6 +6,7 @@
 #include "sa_topk.hpp"
 #include "sa_batch.hpp"
 #include "sa_bm25_params.hpp"
+#include "sa_facet.hpp"
 #include "../../include/searcharray_hip.h"
 
 #include <algorithm>
@@ -156,6 +157,7 @@ void sa_batch_free(sa_batch* bt) {
     if (bt->d_wbase) hipFree(bt->d_wbase);
     if (bt->d_wlen) hipFree(bt->d_wlen);
     if (bt->d_stats) hipFree(bt->d_stats);
+    if (bt->d_facet) hipFree(bt->d_facet);
     if (bt->d_wl) hipFree(bt->d_wl);
     if (bt->d_wl_cnt) hipFree(bt->d_wl_cnt);
     if (bt->d_iota) hipFree(bt->d_iota);
@@ -1302,6 +1304,73 @@ extern "C" int sa_batch_fetch(sa_batch_t* bt, float* scores_out, uint64_t* docs_
             scores_out[(size_t)qi * bt->k + j] = key ? s : 0.f;
             docs_out[(size_t)qi * bt->k + j] = key ? (u64)(u32)(~(u32)(key & 0xFFFFFFFFull)) : SA_NO_DOC;
         }
+    }
+    return SA_OK;
+}
+
+// Part 2d: hit counts and facet counts of the loaded query set under the batch's current filter / minimum-should-match / occur state
+// (header).  One launch of the facet kernel (sa_k_bm25_facet_tiles, sa_bm25.hip) on the batch's stream, behind whatever is in flight:
+// the parameters of an unpruned run over the TF postings -- no impact stream, no bounds, no candidates --, so the matched set is the one
+// a run with k = n_docs would rank.  It reads the slice table (built here if the last fill left it to the staged route: the same launch
+// sa_batch_ensure_tables makes when a run changes route) and the saturation table (built with the batch), and writes its own counters
+// only: the run state, the candidate lists and the results of a run nobody has fetched stay as they are.
+extern "C" int sa_batch_facet_counts(sa_batch_t* bt, sa_codes_t* codes, uint64_t* found_out, uint64_t* missing_out, uint32_t* counts_out) {
+    SA_ARG(bt && bt->ix && found_out, "null argument");
+    if (bt->kind != 0) { sa_set_error("sa_batch_facet_counts: phrase batches have no facet counts"); return SA_ERR_UNSUPPORTED; }
+    sa_index* ix = bt->ix;
+    if (!sa_min_match_tiles(ix->tile_docs)) {
+        sa_set_error("sa_batch_facet_counts: no counting kernel for tile_docs %u (1024, 2048, 4096, 8192)", ix->tile_docs);
+        return SA_ERR_UNSUPPORTED;
+    }
+    const size_t B = bt->B;
+    const size_t V = codes ? codes->n_values : 0;
+    if (codes) {
+        SA_ARG(missing_out && counts_out, "missing_out / counts_out null with a column");
+        SA_ARG(codes->d || codes->n_docs == 0, "null column");
+        SA_ARG(codes->device == ix->device, "the column lives on another device than the batch");
+        SA_ARG(codes->n_docs == ix->n_docs, "the column covers another number of documents than the index holds");
+        SA_ARG((u64)B * V <= SA_FACET_MAX_CELLS, "queries x values of one call must not exceed 2^28");
+    }
+    std::lock_guard<std::mutex> g(ix->mu);
+    SA_HIP(hipSetDevice(ix->device));
+    for (size_t i = 0; i < B; i++) found_out[i] = 0;
+    if (codes) {
+        for (size_t i = 0; i < B; i++) missing_out[i] = 0;
+        memset(counts_out, 0, B * V * sizeof(u32));
+    }
+    // (as sa_batch_launch_route: nothing scores in an empty shard or with an average doc length of 0)
+    if (ix->n_tiles == 0 || ix->n_docs == 0 || ix->avg_doc_len == 0.f) return SA_OK;
+    hipStream_t st = bt->st;
+    const size_t words = 2 * B + B * V;
+    if (bt->facet_words < words) {
+        if (bt->d_facet) {                                      // (no call is in flight: every call waits for its own work)
+            SA_HIP(hipFree(bt->d_facet));
+            bt->d_facet = nullptr; bt->facet_words = 0;
+        }
+        SA_HIP(hipMalloc(&bt->d_facet, words * sizeof(u32)));
+        bt->facet_words = words;
+    }
+    SA_TRY(sa_batch_ensure_bounds(bt, st));
+    const sa_plan pl{};                                     // unpruned, not impact, not seeded: MODE 0 over the TF postings
+    Bm25Params p = sa_batch_params(bt, pl);
+    p.cand = nullptr; p.dense_out = nullptr; p.stats = nullptr; p.no_topk = 0;
+    // (a filtered batch: the tiles in front of the filter's first eligible block are empty for every item)
+    if (bt->filter) p.tile0 = std::min<u32>(bt->filter->first_block / (ix->tile_docs / SA_FILTER_BLOCK), ix->n_tiles);
+    FacetParams fp;
+    fp.codes = codes ? codes->d : nullptr;
+    fp.n_values = (u32)V;
+    fp.found = bt->d_facet; fp.missing = bt->d_facet + B; fp.counts = bt->d_facet + 2 * B;
+    fp.row = bt->d_perm;
+    SA_HIP(hipMemsetAsync(bt->d_facet, 0, words * sizeof(u32), st));
+    SA_TRY(sa_launch_bm25_facet(ix, p, fp, st));
+    SA_HIP(hipGetLastError());
+    std::vector<u32> h(2 * B);
+    SA_HIP(hipMemcpyAsync(h.data(), bt->d_facet, 2 * B * sizeof(u32), hipMemcpyDeviceToHost, st));
+    if (codes && V) SA_HIP(hipMemcpyAsync(counts_out, fp.counts, B * V * sizeof(u32), hipMemcpyDeviceToHost, st));
+    SA_HIP(hipStreamSynchronize(st));
+    for (size_t i = 0; i < B; i++) {
+        found_out[i] = h[i];
+        if (codes) missing_out[i] = h[B + i];
     }
     return SA_OK;
 }

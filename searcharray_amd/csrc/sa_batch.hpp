@@ -110,6 +110,8 @@ struct sa_batch {
     float* d_ub = nullptr;          // [B][T+1] dynamic pruning: score bound of the j smallest-idf terms
     u32* d_ub_order = nullptr;      // [B][T] query-term index of the j-th smallest idf
     u32* d_stats = nullptr;         // diagnostics (sa_batch_stats), null unless enabled
+    u32* d_facet = nullptr;         // counters of sa_batch_facet_counts: [B] found | [B] missing | [B][n_values] counts (grown on demand)
+    size_t facet_words = 0;
     // sparse candidate path (sa_sparse.hip)
     u32* d_lead = nullptr;          // [B] query-term index of the lead term, or 0xFFFFFFFF
     u64* d_p1_off = nullptr;        // [B+1] prefix sums of the lead terms' df

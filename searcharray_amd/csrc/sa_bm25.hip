@@ -19,6 +19,7 @@
 #include "sa_topk.hpp"
 #include "sa_batch.hpp"
 #include "sa_bm25_params.hpp"
+#include "sa_facet.hpp"
 #include "../../include/searcharray_hip.h"
 
 #include <algorithm>
@@ -1057,6 +1058,88 @@ __global__ void __launch_bounds__(THREADS) sa_k_bm25_tiles_list(const Bm25Params
     }
 }
 
+// Facet counts (sa_batch_facet_counts, Part 2d): the tile item with a histogram where the selection is.  One workgroup per
+// (tile, query), the grid of sa_k_bm25_tiles.  The item runs in MODE 0 over the TF postings with neither candidates nor a dense
+// output: it returns behind the minimum-should-match clear and the filter clear, with the tile's final scores in LDS -- exactly the
+// documents that can rank are > 0 -- and a barrier as its last act.  Every thread then walks its E documents: it counts those
+// with a score > 0, reads their category codes (consecutive lanes read consecutive codes) and bumps a bin -- of a workgroup-private
+// LDS histogram for columns of up to SA_FACET_LDS_BINS values, which ALIASES the saturation table (dead behind the last term phase,
+// as sa_tile_topk_hist reuses it: 1024 u32 bins at no extra LDS) and is flushed with one global atomic per non-zero bin; of the
+// query's row of the global counters directly for larger columns.  found / missing: a block sum and one atomic each.
+// An item the tile item's own tests leave (no postings in the tile, an empty filter block, fewer than m terms present, a must term
+// absent) holds zeros only: it finds nothing and returns without touching global memory.  Integer atomics: the result does not depend
+// on their order.  The copy of the parameters with cand / dense_out / stats nulled lets the compiler drop the item's selection code.
+// LDS of an item: the accumulators + spare slots (TILE x 4 + 256 bytes: no selection lists), the match states (MM), the table.
+template <int TILE, int THREADS, int MM>
+__global__ void __launch_bounds__(THREADS) sa_k_bm25_facet_tiles(const Bm25Params p_in, const FacetParams fp) {
+    constexpr size_t ITEM_U64 = sa_tile_smem_u64<TILE, 1>();
+    constexpr int NW = THREADS / SA_WAVE;
+    constexpr int E = TILE / THREADS;
+    static_assert(E <= 32, "a thread's documents fit a 32-bit mask");
+    static_assert((u32)sa_tile_tab_floats<THREADS, false>() >= SA_FACET_LDS_BINS, "the LDS histogram aliases the saturation table");
+    typedef typename sa_match_state<MM>::type mc_t;
+    __shared__ alignas(16) u64 smem[ITEM_U64 + (MM ? (TILE + SA_WAVE) * sizeof(mc_t) / 8 : 0)];
+    __shared__ float s_tab[sa_tile_tab_floats<THREADS, false>()];
+    __shared__ u32 f_red[NW + 1];
+    __shared__ u32 f_miss;
+    const u32 tile = p_in.tile0 + blockIdx.z * SA_GRID_Y + blockIdx.y;
+    if (tile >= p_in.tile_end) return;
+    Bm25Params p = p_in;
+    p.cand = nullptr; p.dense_out = nullptr; p.stats = nullptr; p.qlist = nullptr;
+    const u32 q = blockIdx.x;
+    if constexpr (MM != 0) sa_bm25_tile_item<TILE, THREADS, 0, false, MM>(p, tile, q, smem, s_tab, (mc_t*)(smem + ITEM_U64));
+    else sa_bm25_tile_item<TILE, THREADS, 0, false>(p, tile, q, smem, s_tab);
+    // (the item's last act is a barrier: the scores are final and the table is dead)
+    const u32 tid = threadIdx.x;
+    const float* const acc = (const float*)smem;
+    const u64 tile_base = (u64)tile * TILE;
+    const u64 remain = p.n_docs - tile_base;
+    const u32 tile_n = remain < (u64)TILE ? (u32)remain : (u32)TILE;
+    u32 mine = 0;                                               // bit j: document j * THREADS + tid of the tile matched
+#pragma unroll
+    for (int j = 0; j < E; j++) {
+        const u32 e = j * THREADS + tid;
+        if (e < tile_n && acc[e] > 0.f) mine |= 1u << j;
+    }
+    const u32 n_found = sa_block_sum<NW>((u32)__popc(mine), f_red);
+    if (n_found == 0u) return;                                  // (uniform) nothing matched: no global access
+    const u32 row = fp.row[q];
+    if (!fp.codes) {                                            // (uniform) found only
+        if (tid == 0) atomicAdd(&fp.found[row], n_found);
+        return;
+    }
+    const u32 nv = fp.n_values;
+    const bool lds = nv <= SA_FACET_LDS_BINS;                   // (uniform)
+    u32* const bins = (u32*)s_tab;
+    u32* const grow = fp.counts + (u64)row * nv;
+    if (lds) for (u32 i = tid; i < nv; i += THREADS) bins[i] = 0u;
+    if (tid == 0) f_miss = 0u;
+    __syncthreads();
+    u32 miss = 0;
+#pragma unroll
+    for (int j = 0; j < E; j++) {
+        if ((mine >> j) & 1u) {
+            const int c = fp.codes[tile_base + (u32)(j * THREADS) + tid];
+            if (c < 0) miss++;
+            else if (lds) atomicAdd(&bins[c], 1u);
+            else atomicAdd(&grow[c], 1u);
+        }
+    }
+    miss = sa_wave_sum(miss);
+    if (sa_lane() == 0 && miss) atomicAdd(&f_miss, miss);
+    __syncthreads();
+    if (lds) {
+        for (u32 i = tid; i < nv; i += THREADS) {
+            const u32 c = bins[i];
+            if (c) atomicAdd(&grow[i], c);
+        }
+    }
+    if (tid == 0) {
+        atomicAdd(&fp.found[row], n_found);
+        if (f_miss) atomicAdd(&fp.missing[row], f_miss);
+    }
+}
+
 // ---------------------------------------------------------------------------------------------
 // Grouped exhaustive scoring: queries of a batch that share their FIRST term.
 //
@@ -1954,6 +2037,36 @@ int sa_launch_bm25_list(sa_index* ix, const Bm25Params& p, hipStream_t st) {
             sa_set_error("unsupported tile_docs %u for the query-list scan", ix->tile_docs);
             return SA_ERR_STATE;
     }
+    return SA_OK;
+}
+
+// the facet pass over p's tiles and rows: the grid of sa_launch_bm25_mode, the MM the batch's counting state asks for.
+// Workgroup sizes: TWICE those of sa_k_bm25_tiles for the same tile (16 documents per thread, 4 at 1024), on purpose -- an
+// instantiation of the tile item that an existing kernel uses too would share the item's function-local LDS variables with it, and
+// the compiler then allocates that kernel's registers differently (measured: the MODE 0 instantiations of 2048 docs and up came out
+// with other VGPR counts).  With sizes of its own the pre-existing kernels' gfx950 code is what it was, instruction for instruction.
+int sa_launch_bm25_facet(sa_index* ix, const Bm25Params& p, const FacetParams& fp, hipStream_t st) {
+    if (ix->n_tiles == 0 || p.nq == 0 || p.tile_end <= p.tile0) return SA_OK;
+    const u32 nt = p.tile_end - p.tile0;
+    const u32 gy = nt < SA_GRID_Y ? nt : SA_GRID_Y;
+    const dim3 grid(p.nq, gy, (nt + SA_GRID_Y - 1) / SA_GRID_Y);
+#define SA_LAUNCH_FACET(TILE, THREADS)                                                                                            \
+    {                                                                                                                             \
+        if (p.occur_off) hipLaunchKernelGGL((sa_k_bm25_facet_tiles<TILE, THREADS, 2>), grid, dim3(THREADS), 0, st, p, fp);         \
+        else if (p.min_match_off) hipLaunchKernelGGL((sa_k_bm25_facet_tiles<TILE, THREADS, 1>), grid, dim3(THREADS), 0, st, p, fp); \
+        else hipLaunchKernelGGL((sa_k_bm25_facet_tiles<TILE, THREADS, 0>), grid, dim3(THREADS), 0, st, p, fp);                     \
+    }                                                                                                                             \
+    break
+    switch (ix->tile_docs) {
+        case 1024: SA_LAUNCH_FACET(1024, 256);
+        case 2048: SA_LAUNCH_FACET(2048, 128);
+        case 4096: SA_LAUNCH_FACET(4096, 256);
+        case 8192: SA_LAUNCH_FACET(8192, 512);
+        default:
+            sa_set_error("facet counts: no counting kernel for tile_docs %u (1024, 2048, 4096, 8192)", ix->tile_docs);
+            return SA_ERR_UNSUPPORTED;
+    }
+#undef SA_LAUNCH_FACET
     return SA_OK;
 }
 

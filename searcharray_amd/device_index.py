@@ -10,7 +10,7 @@ from __future__ import annotations
 import ctypes
 import os
 import weakref
-from typing import Optional, Sequence, Tuple
+from typing import NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -440,6 +440,24 @@ class DeviceIndex(_options.OptionsMixin):
         self._call("sa_filter_create_from_term", self._h, t if 0 <= t < self.n_terms else NO_TERM, ctypes.byref(h))
         return DocFilter(self, h)
 
+    def facet_column(self, codes, n_values: int) -> "FacetColumn":
+        """A categorical column on this index's device (``sa_codes_create``) for ``QueryBatch.facet_counts`` / ``DeviceVec.facet_counts``:
+        one integer code per local doc, -1 = no value (pandas' code for NaN), else in ``[0, n_values)``; 1 <= n_values <= 2**20."""
+        c = np.asarray(codes)
+        if c.ndim != 1 or (c.size and c.dtype.kind not in "iu"):
+            raise ValueError("facet codes: a 1-d integer array, one code per document")
+        if c.shape[0] != self.n_docs:
+            raise ValueError(f"a facet column has one code per document ({self.n_docs}), got {c.shape[0]}")
+        n_values = int(n_values)
+        if not 1 <= n_values <= 1 << 20:
+            raise ValueError("n_values must be in 1 .. 2**20")
+        if c.size and (int(c.min()) < -1 or int(c.max()) >= n_values):
+            raise ValueError(f"facet codes must be -1 (no value) or in [0, {n_values})")
+        c32 = np.ascontiguousarray(c, dtype=np.int32)
+        h = ctypes.c_void_p()
+        self._call("sa_codes_create", self._h, c32.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), self.n_docs, n_values, ctypes.byref(h))
+        return FacetColumn(self, h, n_values)
+
     def queue(self, n_queries: int, n_terms: int, k: int = 10, k1: float = 1.2, b: float = 0.75, depth: int = 6, opts=None) -> "QueryQueue":
         """a query-set queue (``sa_queue_*``): ``depth`` batches of ``n_queries`` x ``n_terms`` behind one handle, stepped by a worker
         thread of the library; needs ``set_idf_table`` first"""
@@ -540,6 +558,43 @@ class DocFilter:
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
             self.api.sa_filter_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class FacetCounts(NamedTuple):
+    """what ``SearchArray.facets`` (one entry per query) and ``solr.edismax_facets`` (one query: scalars and one row) return"""
+    found: object            # int64[B] (or int): rows that matched -- Solr's numFound
+    missing: object          # int64[B] (or int): those of them without a value in the column
+    counts: object           # int64[B, V] (or int64[V]): those with each value
+    categories: object       # the values the V codes stand for (a pandas Index), or None
+
+
+class FacetColumn:
+    """A column of category codes on the device (``sa_codes_*``; ``DeviceIndex.facet_column`` builds one): what
+    ``QueryBatch.facet_counts`` and ``DeviceVec.facet_counts`` count over.  It belongs to a device and a number of documents, like a
+    ``DocFilter``.  ``categories``: the values the codes stand for, if the caller attached them (``SearchArray.facet_column``)."""
+
+    def __init__(self, index: "DeviceIndex", handle, n_values: int, categories=None):
+        self.index = index
+        self.api = index.api
+        self._h = handle
+        self.n_values = int(n_values)
+        self.categories = categories
+
+    def _need(self):
+        if self._h is None or not self._h.value:
+            raise ValueError("the FacetColumn is closed")
+        return self._h
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self.api.sa_codes_destroy(self._h)
             self._h = ctypes.c_void_p()
 
     def __del__(self):
@@ -673,6 +728,23 @@ class QueryBatch(_options.OptionsMixin):
         docs = np.empty((self.B, self.k), dtype=np.uint64)
         self._call("sa_batch_fetch", self._h, p_f32(scores), p_u64(docs))
         return scores, docs
+
+    def facet_counts(self, column: Optional["FacetColumn"] = None):
+        """Hit counts and facet counts of the loaded query set under the batch's current filter / min_match / occur state, counted
+        on the device (``sa_batch_facet_counts``): ``(found int64[B], missing int64[B], counts int64[B, V] | None)`` in caller order.
+        ``found[i]``: docs with a score > 0 -- what ``fetch`` could return for k = n_docs; ``missing[i]``: those of them without a
+        value in ``column``; ``counts[i, c]``: those with code c.  ``column=None``: ``found`` alone (missing is zeros, counts None).
+        Synchronous; a run that has not been fetched returns the same results afterwards."""
+        if column is not None and not isinstance(column, FacetColumn):
+            raise TypeError("facet_counts takes a FacetColumn or None")
+        found = np.zeros(self.B, dtype=np.uint64)
+        missing = np.zeros(self.B, dtype=np.uint64)
+        if column is None:
+            self._call("sa_batch_facet_counts", self._h, None, p_u64(found), None, None)
+            return found.astype(np.int64), missing.astype(np.int64), None
+        counts = np.zeros((self.B, column.n_values), dtype=np.uint32)
+        self._call("sa_batch_facet_counts", self._h, column._need(), p_u64(found), p_u64(missing), p_u32(counts))
+        return found.astype(np.int64), missing.astype(np.int64), counts.astype(np.int64)
 
     def profile(self) -> Tuple[float, int, int]:
         ms = _lib.c_double(0)
@@ -990,6 +1062,22 @@ class DeviceVec:
         self.api.call("sa_vec_topk", self._h, filter._need() if filter is not None else None, k,
                       scores.ctypes.data_as(ctypes.c_void_p), p_u64(rows), ctypes.byref(found))
         return scores, rows, int(found.value)
+
+    def facet_counts(self, column: Optional["FacetColumn"], filter: Optional["DocFilter"] = None):
+        """``(found, missing, counts int64[V])`` over the entries ``topk`` could rank -- value > 0 (NaN never), inside ``filter`` --,
+        counted on the device in one pass (``sa_vec_facet_counts``); ``column=None``: ``(found, 0, None)``."""
+        if column is not None and not isinstance(column, FacetColumn):
+            raise TypeError("facet_counts takes a FacetColumn or None")
+        if filter is not None and not isinstance(filter, DocFilter):
+            raise TypeError("filter must be a DocFilter")
+        found, missing = _lib.c_uint64(0), _lib.c_uint64(0)
+        fh = filter._need() if filter is not None else None
+        if column is None:
+            self.api.call("sa_vec_facet_counts", self._h, fh, None, ctypes.byref(found), None, None)
+            return int(found.value), 0, None
+        counts = np.zeros(column.n_values, dtype=np.uint32)
+        self.api.call("sa_vec_facet_counts", self._h, fh, column._need(), ctypes.byref(found), ctypes.byref(missing), p_u32(counts))
+        return int(found.value), int(missing.value), counts.astype(np.int64)
 
     def topk_passes(self) -> int:
         """passes over the vector the last ``topk`` made (diagnostics)"""

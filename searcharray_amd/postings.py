@@ -910,6 +910,110 @@ class SearchArray(ExtensionArray):
             if own is not None:
                 own.close()
 
+    # -- hit counts and facet counts (Solr's numFound and facet.field; no counterpart in the reference)
+    def facet_column(self, values, n_values: Optional[int] = None):
+        """A categorical column of the array's rows on the device, for :meth:`facets` and ``solr.edismax_facets``: a pandas
+        ``Categorical``, a Series of category dtype (its ``.categories`` are kept), or an integer code array (-1 = no value;
+        ``n_values`` defaults to ``max + 1``).  A ``FacetColumn``: reusable, ``close()`` releases it."""
+        if self._rows is not None:
+            raise ValueError("facet columns are built on the whole indexed array, not on a slice")
+        categories = None
+        if isinstance(values, pd.Series) and isinstance(values.dtype, pd.CategoricalDtype):
+            values = values.array
+        if isinstance(values, pd.Categorical):
+            categories = values.categories
+            codes = np.asarray(values.codes)
+            if n_values is None:
+                n_values = max(1, len(categories))
+        else:
+            if isinstance(values, pd.Series):
+                values = values.to_numpy()
+            codes = np.asarray(values)
+            if codes.ndim != 1 or (codes.size and codes.dtype.kind not in "iu"):
+                raise ValueError("facet_column: a pandas Categorical, a Series of category dtype, or a 1-d integer code array")
+            if n_values is None:
+                n_values = max(1, int(codes.max()) + 1) if codes.size else 1
+        n = len(self._core.doc_lens)
+        if codes.shape[0] != n:
+            raise ValueError(f"a facet column needs one entry per row ({n}), got {codes.shape[0]}")
+        col = self._core.device().facet_column(codes, int(n_values))
+        col.categories = categories
+        return col
+
+    def facets(self, queries, by, filter=None, mm=None, q_op: str = "OR", occur=None, similarity=default_bm25):
+        """Per query, how the rows it matches spread over a categorical column -- Solr's ``facet.field`` --, counted on the device:
+        ``FacetCounts(found int64[B], missing int64[B], counts int64[B, V], categories)``.  ``by``: a column from
+        :meth:`facet_column`, or anything it takes.  The matched rows are exactly those ``search(queries, k=len(arr), ...)`` would
+        return under the same ``filter`` / ``mm`` / ``q_op`` / ``occur`` (same argument handling): ``found`` counts them,
+        ``missing`` those of them without a value, ``counts[i, c]`` those with value c; ``counts.sum(1) + missing == found``."""
+        from .device_index import FacetColumn, FacetCounts
+        own = None
+        if not isinstance(by, FacetColumn):
+            by = own = self.facet_column(by)
+        try:
+            if by.index is not self._core.device():
+                raise ValueError("the facet column was built for another index")
+            found, missing, counts = self._counted(queries, by, filter, mm, q_op, occur, similarity)
+            return FacetCounts(found, missing, counts, by.categories)
+        finally:
+            if own is not None:
+                own.close()
+
+    def count(self, queries, filter=None, mm=None, q_op: str = "OR", occur=None, similarity=default_bm25) -> np.ndarray:
+        """Per query, the number of rows it matches (Solr's ``numFound``; ``facets(...).found`` without a column), int64[B]"""
+        return self._counted(queries, None, filter, mm, q_op, occur, similarity)[0]
+
+    def _counted(self, queries, column, filter, mm, q_op, occur, similarity):
+        """(found, missing, counts) of ``facets`` / ``count``: the batch ``search`` would run, counted instead of ranked"""
+        if getattr(similarity, "kind", None) != "bm25":
+            raise ValueError("batched search needs a stock BM25 similarity (bm25_similarity(k1, b))")
+        if self._rows is not None:
+            raise ValueError("batched search runs on the whole indexed array, not on a slice")
+        toks, classes = self._occur_arg(queries, occur)
+        B = len(toks)
+        from .device_index import DocFilter
+        fmask = frows = None
+        if filter is not None and not isinstance(filter, DocFilter):
+            fmask, frows = self._filter_arg(filter)                 # (checked before anything is launched)
+        n_should = [len(q) if classes is None else sum(c == 0 for c in classes[i]) for i, q in enumerate(toks)]
+        need = self._min_match_arg(mm, q_op, n_should)
+        if classes is not None and not any(c for cl in classes for c in cl):
+            classes = None
+        V = None if column is None else column.n_values
+        if B == 0 or len(self._core.doc_lens) == 0:
+            z = np.zeros(B, dtype=np.int64)
+            return z, z.copy(), None if V is None else np.zeros((B, V), dtype=np.int64)
+        dev = self._core.device()
+        unknown = dev.n_terms                                   # any id >= n_terms matches nothing
+        ids = [[t if (t := self._term_id(tok)) >= 0 else unknown for tok in q] for q in toks]
+        T = max(1, max(len(q) for q in ids))
+        mat = np.full((B, T), unknown, dtype=np.int64)
+        for i, q in enumerate(ids):
+            mat[i, :len(q)] = q
+        batch = dev.batch(mat, k=1, k1=similarity.k1, b=similarity.b)
+        own = None
+        try:
+            if need is not None and int(need.max()) > (1 if classes is None else 0):
+                batch.set_min_match(need)
+            if classes is not None:
+                occ = np.zeros(mat.shape, dtype=np.uint8)
+                for i, cl in enumerate(classes):
+                    occ[i, :len(cl)] = cl
+                batch.set_occur(occ)
+            if filter is not None:
+                if isinstance(filter, DocFilter):
+                    if filter.index is not dev:
+                        raise ValueError("the filter was built for another index")
+                    f = filter
+                else:
+                    f = own = dev.doc_filter(mask=fmask) if fmask is not None else dev.doc_filter(rows=frows)
+                batch.set_filter(f)
+            return batch.facet_counts(column)
+        finally:
+            batch.close()
+            if own is not None:
+                own.close()
+
     def positions(self, token: str, key=None) -> List[np.ndarray]:
         """positions of ``token`` per doc (reference postings.py:682-687)."""
         tid = self.term_dict.get_term_id(token)

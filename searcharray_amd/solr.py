@@ -19,7 +19,8 @@ through both).  Anything else -- custom similarity callables, slices -- takes th
 
 ``edismax_search`` (no counterpart in the reference, whose callers rank the dense result with ``np.argpartition``) returns the
 top ``k`` rows of the same scores, optionally inside a document filter (Solr's ``fq``): on the device route the combined vector
-is selected in HBM (``sa_vec_topk``, csrc/sa_vec_topk.hip) and never crosses PCIe.
+is selected in HBM (``sa_vec_topk``, csrc/sa_vec_topk.hip) and never crosses PCIe.  ``edismax_facets`` counts the same vector
+instead of ranking it -- Solr's ``facet.field`` for one query (``sa_vec_facet_counts``, csrc/sa_facet.hip).
 """
 from __future__ import annotations
 
@@ -31,7 +32,7 @@ from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple, Union
 import numpy as np
 import pandas as pd
 
-from .device_index import NO_DOC, DocFilter
+from .device_index import NO_DOC, DocFilter, FacetColumn, FacetCounts
 from .postings import SearchArray
 from .similarity import Similarity, default_bm25
 
@@ -569,6 +570,75 @@ def edismax_search(frame: pd.DataFrame,
         comb.close()
         if own is not None:
             own.close()
+
+
+def edismax_facets(frame: pd.DataFrame,
+                   q: str,
+                   qf: List[str],
+                   by,
+                   fq=None,
+                   mm: Optional[Union[str, int]] = None,
+                   pf: Optional[List[str]] = None,
+                   pf2: Optional[List[str]] = None,
+                   pf3: Optional[List[str]] = None,
+                   tie: float = 0.0,
+                   q_op: str = "OR",
+                   similarity: Union[Similarity, Dict[str, Similarity]] = default_bm25,
+                   use_device: Optional[bool] = None) -> FacetCounts:
+    """Solr's ``facet.field`` for one :func:`edismax` query: how the rows it matches (score > 0, inside ``fq``) spread over a
+    categorical column.  ``by``: a ``FacetColumn`` built from any ``SearchArray`` column of the frame
+    (``arr.facet_column(frame.brand)``), or anything ``facet_column`` takes.  Returns ``FacetCounts(found, missing, counts
+    int64[V], categories)``; ``found`` equals ``edismax_search(...).found`` for the same arguments.  On the device route the
+    combined vector is counted in HBM (``sa_vec_facet_counts``): two counters and V counts cross PCIe.  Where the combination
+    takes the host route (custom similarities, slices) the same numbers come from ``np.bincount`` over the host scores."""
+    plan = _plan(frame, q, qf, mm, pf, pf2, pf3, q_op, similarity)
+    if use_device is None:
+        use_device = _DeviceCombiner.usable(plan.fields, len(frame))
+    n = len(frame)
+    if not use_device:
+        if isinstance(by, FacetColumn):
+            raise ValueError("the host route counts over host codes: pass the column's values, not a FacetColumn")
+        if isinstance(by, pd.Series) and isinstance(by.dtype, pd.CategoricalDtype):
+            by = by.array
+        categories = by.categories if isinstance(by, pd.Categorical) else None
+        codes = np.asarray(by.codes if isinstance(by, pd.Categorical) else by)
+        if codes.shape != (n,) or (codes.size and codes.dtype.kind not in "iu"):
+            raise ValueError(f"a facet column needs one integer code per row ({n})")
+        n_values = max(1, len(categories)) if categories is not None else (max(1, int(codes.max()) + 1) if codes.size else 1)
+        if codes.size and int(codes.min()) < -1:
+            raise ValueError("facet codes must be -1 (no value) or >= 0")
+        mask = _fq_mask(frame, fq)
+        scores, _ = _host_scores(frame, plan, tie)
+        keep = scores > 0
+        if mask is not None:
+            keep &= mask
+        counts = np.bincount(codes[keep & (codes >= 0)], minlength=n_values).astype(np.int64)
+        return FacetCounts(int(keep.sum()), int((keep & (codes < 0)).sum()), counts, categories)
+    own = own_col = None
+    if fq is None or isinstance(fq, DocFilter):
+        filt = fq
+        if filt is not None and filt.index.n_docs != n:
+            raise ValueError(f"fq covers {filt.index.n_docs} documents, the frame has {n} rows")
+    else:
+        mask = _fq_mask(frame, fq)         # (checked before anything is launched)
+        filt = own = plan.fields[0].array._core.device().doc_filter(mask=mask)
+    comb = None
+    try:
+        if not isinstance(by, FacetColumn):
+            by = own_col = plan.fields[0].array.facet_column(by)
+        elif by.index.n_docs != n:
+            raise ValueError(f"the facet column covers {by.index.n_docs} documents, the frame has {n} rows")
+        comb = _DeviceCombiner(plan.fields, n)
+        scores_v, _ = _device_scores(comb, plan, tie)
+        found, missing, counts = scores_v.facet_counts(by, filter=filt)
+        return FacetCounts(found, missing, counts, by.categories)
+    finally:
+        if comb is not None:
+            comb.close()
+        if own is not None:
+            own.close()
+        if own_col is not None:
+            own_col.close()
 
 
 _BATCH_MAX_FIELDS = 8           # a fields batch spans at most this many columns (sa_fields_batch_create)
